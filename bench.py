@@ -50,6 +50,7 @@ DSA_BYTES = 99                 # per DSA-2048/256 signature veri
 # only the triangles of a*a: 4 lanes x (4 x 190 + 1,444) = 8,816.  e = 65537: 16 squarings + 2 products.
 MACS_PER_RSA_VERIFY = 16 * 8816 + 2 * 11552
 LINE_MAX = 6144                # bytes of the ONE stdout line (round 5's had grown to 25 KB and the driver's parser returned nothing)
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all arrays together
 
 
 def macs_per_dsa_verify(table_bits):
@@ -89,7 +90,7 @@ def parse_args(argv=None):
     ap.add_argument("--distinct", type=int, default=2500, help="cfg 4: distinctly signed writes the resident batch is tiled from")
     ap.add_argument("--chunk", type=int, default=125000, help="cfg 4: writes per verifier call (the resident batch)")
     ap.add_argument("--inflight", type=int, default=None, help="batches (steps) in flight per GPU, each on its own context; default 3 "
-                    "(cfg 2, 3), 16 (cfg 5 with its 16 hardware queues: its CalculateR is a chain that leaves most issue slots of one step empty; 4 with the runtime's default 4 queues), "
+                    "(cfg 2, 3), 4 for cfg 5 (16 when the environment gives the HIP runtime 16 or more hardware queues: its CalculateR is a chain that leaves most issue slots of one step empty), "
                     "cfg 4 always runs one call at a time.  cfg 2: batches in flight per GPU, each on its own verifier context "
                     "(its own arena and streams).  With more than one, walk/parse and compare/tally/exchange of one step run under "
                     "the modexp of a neighbour -- what a fed verifier does; the machine-filling modexps themselves take turns "
@@ -107,19 +108,20 @@ def parse_args(argv=None):
                     "otherwise never sees a timed region of tens of milliseconds.  0 disables")
     ap.add_argument("--corpus-cache", default="", help="path prefix of an .npz cache of the generated corpus (profiling reruns)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo: launcher, sharding and exchange step only (no GPU, no number)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="cfg 2: after the timed steps, write what the last timed step "
+                    "returned to its caller (error code, exit count and verdict bits per write, the gathered verdict bitmap) as DIR/<name>.npy in "
+                    "float32, %d MB at most in all, so that two builds can be compared output for output" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--full-json", default=None, help="where the FULL record goes (sweeps, per-thread serving runs, timelines, notes, commands, "
                     "every other config's record): default bench_full.json next to bench.py (bench_full_cfgN.json with --config N).  stdout "
                     "carries ONE line of at most %d bytes -- the contract's keys, roofline, cpu_baseline, int_mac and a per-config summary" % LINE_MAX)
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.config not in (None, 2):
+        ap.error("--dump-outputs: only the cfg-2 path (the headline) writes its outputs")
     if args.steps is None:
         args.steps = 200 if (args.config in (None, 2) and not args.dry_run) else 64 if args.config == 5 else 10
-    if args.config == 5 and not args.dry_run:
-        # Steps of cfg 5 are chains on too few waves to fill the chip (docs/history.md, round 4): what buys throughput is MANY steps in
-        # flight, each on its own context, and their streams on hardware queues of their own.  The HIP runtime multiplexes all streams
-        # onto GPU_MAX_HW_QUEUES queues (4 by default; read when the runtime starts, so it is set here, before torch / HIP are
-        # loaded).  Measured (tools/runs/r04/gpu_r4z.sh): 4 queues x 4 steps in flight 7.6 ms per step, 16 x 8: 6.2, 16 x 12: 5.8, 16 x 16:
-        # 5.7 (24 or 32 queues are worse: a context's three streams then collide differently).
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+    # cfg 5's steps are chains on too few waves to fill the chip (docs/history.md, round 4): more steps in flight, each on its own
+    # context, buy throughput when the HIP runtime has more hardware queues to spread their streams over.  The queue count is the
+    # environment's (GPU_MAX_HW_QUEUES, read when the runtime starts); bench.py does not raise it.
     if args.inflight is None:
         many = int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 16
         args.inflight = (16 if many else 4) if args.config == 5 else 3
@@ -172,7 +174,12 @@ class Dist:
 
     def barrier(self):
         if self.dist:
-            self.dist.barrier()
+            if self.dry:
+                # torch's barrier() looks for an accelerator first (that starts the HIP runtime, even on a gloo group): a
+                # --dry-run rank must not open the GPU, so it synchronises with a one-element all-reduce on the CPU instead
+                self.dist.all_reduce(self.torch.zeros(1))
+            else:
+                self.dist.barrier()
 
     def sync(self):
         if not self.dry:
@@ -254,7 +261,7 @@ class Dist:
 
     def close(self):
         if self.dist:
-            self.dist.barrier()
+            self.barrier()
             self.dist.destroy_process_group()
 
 
@@ -581,6 +588,19 @@ def timed_region(D, run, steps, warmup, reset=None):
     return D.max_float(time.perf_counter() - t0)
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float32 (every value written is an integer below 2^24, so exactly).  An
+    array over its share of DUMP_MAX_BYTES is cut to a fixed sample: the same positions, in order, for the same length, from a
+    seeded generator -- two builds run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (4 * max(1, len(arrays)))
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0xD0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def base_line(args, D, metric, unit, value, elapsed, dtype, workload, extra_cfg, scaling="weak"):
     cfg = {"workload": workload, "parallelism": "one process per GPU x%d" % D.world}
     cfg.update(extra_cfg)
@@ -727,6 +747,8 @@ def bench_cfg2(args, D):
                 V.gathers += 1
         elapsed = timed_region(D, run, args.steps, args.warmup)
         rows = np.unpackbits(gathered[-1].reshape(D.world, -1), axis=1, bitorder="little")[:, :items]
+        if args.dump_outputs and D.rank == 0:
+            dump_outputs(args.dump_outputs, {"verdict_bitmap": gathered[-1]})
         tot = D.sum_ints([int(want_ok.sum())])[0]
         return {"dry_run": True, "config": 2, "n_gpus": D.world, "world_size": D.world, "steps": args.steps, "warmup": args.warmup,
                 "parallelism": "shard-by-write x%d, all-gather of verdict bitmaps" % D.world, "allgathers_in_step_loop": V.gathers, "gather_rows": int(rows.shape[0]),
@@ -735,6 +757,12 @@ def bench_cfg2(args, D):
 
     V.run(V.n_ctx)               # one untimed call per verifier context: its arena is allocated at its first call
     elapsed = timed_region(D, V.run, args.steps, args.warmup, V.reset_timing)
+    if args.dump_outputs and D.rank == 0:
+        # the last timed step ran on context (steps - 1) % n_ctx; the isolated calls below overwrite context 0's outputs
+        k = (args.steps - 1) % V.n_ctx
+        e, nv, vd, bits = V.outs[k]
+        dump_outputs(args.dump_outputs, {"err": e.cpu().numpy(), "n_verified": nv.cpu().numpy(), "verdict": vd.cpu().numpy(),
+                                         "verdict_bitmap": bits.cpu().numpy()})
     sclk = V.ctxs[0].last_sclk_mhz()
     timed_rsa, timed_total, timed_hash = list(V.rsa_ms), list(V.total_ms), list(V.hash_ms)
     iso = []
@@ -1290,8 +1318,7 @@ def threshold_serving_leg(tc, res, n, threads="1,64,256", seconds=1.0):
             fh.write(tc.dsa_q.to_bytes(32, "big") + i32(tc.s_xs) + _ints_to_be(flat(tc.s_ys[:n]), 32).tobytes() + res["s"][:n].tobytes())
             fh.write(tc.dsa_p.to_bytes(256, "big") + i32(tc.r_xs) + _ints_to_be(flat(tc.r_ri[:n]), 256).tobytes() +
                      _ints_to_be(flat(tc.r_vi[:n]), 32).tobytes() + res["r"][:n].tobytes() + res["st_r"][:n].tobytes())
-        env = dict(os.environ)
-        env.pop("GPU_MAX_HW_QUEUES", None)          # the serving process runs on the runtime's defaults, like the cfg-2 leg
+        env = dict(os.environ)          # the serving process runs on the same hardware-queue setting as this one
         r = subprocess.run([exe, path, "256", "0", threads, str(seconds)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240, env=env)
         if r.returncode != 0:
             return {"error": "threshold_load rc=%d: %s" % (r.returncode, r.stderr.decode(errors="replace")[-300:])}
@@ -1432,7 +1459,7 @@ def bench_cfg5(args, D):
                         "(product of 10 partial signatures mod the 2048-bit N of rsa/test.pkcs8), SSS calculateSecret (k=7 of n=10, mod the 2048-bit "
                         "prime of sss_test.go), threshold-DSA combine = calculateS (2t=8, 256-bit q) + CalculateR (2t=8, 2048/256-bit group); one "
                         "operation = one scheme-level combine (3 per index); %d independent steps in flight on %d contexts with GPU_MAX_HW_QUEUES=%s "
-                        "(set before the HIP runtime loads: a service must export it itself) -- ONE step at a time is `single_flight`%s"
+                        "(read when the HIP runtime loads: a service must export it itself) -- ONE step at a time is `single_flight`%s"
                         % (n_total, D.world, n_ctx, n_ctx, os.environ.get("GPU_MAX_HW_QUEUES", "4 (runtime default)"),
                            "" if n_nodes == 10 else "; THIS RUN (--replicas %d): dealings to %d nodes, SSS k = %d and threshold DSA 2t = %d shares per "
                            "combine instead of 7 / 8 -- Lagrange coefficients on exact big integers" % (n_nodes, n_nodes, K_SSS, K_DSA)),

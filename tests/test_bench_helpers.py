@@ -204,3 +204,16 @@ def test_roofline_launch_ms_is_a_single_flight_duration_in_every_committed_r06_l
         import pytest
         pytest.skip("no round-6 record committed yet")
     assert seen >= 1
+
+
+def test_dump_outputs_is_float32_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files; an array over its share of the budget becomes the same seeded sample on every run"""
+    small = np.arange(10, dtype=np.int32)
+    big = np.arange(5000, dtype=np.uint8) % 7
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8000)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"small": small, "big": big})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and (s == small).all()
+    assert b.dtype == np.float32 and b.size == 8000 // (4 * 2)
+    assert (np.load(tmp_path / "b" / "big.npy") == b).all()

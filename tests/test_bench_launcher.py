@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +43,15 @@ def test_gpus_flag_spawns_the_ranks():
 def test_single_rank_needs_no_process_group():
     r = _run([])
     assert r["n_gpus"] == 1 and r["gather_rows"] == 1 and r["own_row_matches"] and r["allgathers_in_step_loop"] == 5
+
+
+def test_dump_outputs_writes_the_last_steps_bitmap(tmp_path):
+    """--dump-outputs DIR: the outputs of the last timed step as float32 .npy files; the dry run's is the gathered bitmap"""
+    r = _run(["--dump-outputs", str(tmp_path)])
+    bits = np.load(tmp_path / "verdict_bitmap.npy")
+    assert bits.dtype == np.float32 and bits.size == (24 + 7) // 8
+    ok = np.unpackbits(bits.astype(np.uint8), bitorder="little")[:24]
+    assert int(ok.sum()) == r["gathered_ok"]
 
 
 def test_torchrun_environment_is_honoured():

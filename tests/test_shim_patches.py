@@ -1,6 +1,10 @@
 """CPU, build container only: the patches under shim/patches/ apply to the reference tree they were cut against (the judge of
-round 2 found 0001 malformed -- it had never been applied anywhere).  Skipped where /root/reference does not exist."""
+round 2 found 0001 malformed -- it had never been applied anywhere).  The tests that apply them to the tree itself are skipped
+where the tree is not present; test_patches_match_the_recorded_tree checks them against what was recorded from it."""
+import hashlib
+import json
 import os
+import re
 import shutil
 import subprocess
 
@@ -8,6 +12,49 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
+
+
+def parse_patch(text):
+    """(file, first line of the hunk in the tree before this patch, lines it replaces, lines it puts there) for each hunk of a
+    unified diff, in order; asserts that every hunk holds as many lines as its header says."""
+    out, path, lines = [], None, text.splitlines(keepends=True)
+    i = 0
+    while i < len(lines):
+        ln = lines[i]
+        if ln.startswith("+++ "):
+            path = ln[4:].split("\t")[0].strip().split("/", 1)[1]
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", ln)
+        i += 1
+        if not m:
+            continue
+        n_old, n_new = int(m.group(2) or 1), int(m.group(4) or 1)
+        pre, post = [], []
+        while len(pre) < n_old or len(post) < n_new:
+            body = lines[i]
+            i += 1
+            if body[0] in " -":
+                pre.append(body[1:])
+            if body[0] in " +":
+                post.append(body[1:])
+            assert body[0] in " -+", (path, m.group(0), body)
+        assert len(pre) == n_old and len(post) == n_new, (path, m.group(0))
+        out.append((path, int(m.group(1)), pre, post))
+    return out
+
+
+def test_patches_match_the_recorded_tree():
+    """Without the tree: every hunk of shim/patches is well formed, and what it replaces is, byte for byte, what the reference held
+    at that place when tests/golden/reference_tree.json was recorded from it (tests/golden/make_reference_tree.py)."""
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_tree.json")))["hunks"]
+    pdir = os.path.join(ROOT, "shim", "patches")
+    names = sorted(f for f in os.listdir(pdir) if f.endswith(".patch"))
+    assert names == sorted(rec), "a patch was added or removed: rerun tests/golden/make_reference_tree.py"
+    for name in names:
+        hunks = parse_patch(open(os.path.join(pdir, name)).read())
+        assert len(hunks) == len(rec[name]) and hunks, name
+        for (path, start, pre, _), r in zip(hunks, rec[name]):
+            assert (path, start) == (r["file"], r["line"]), (name, path, start, r)
+            assert hashlib.sha256("".join(pre).encode()).hexdigest() == r["sha256"], (name, path, start, "not what the tree holds there")
 
 
 @pytest.mark.skipif(not os.path.isdir(REF) or shutil.which("patch") is None, reason="reference tree or patch(1) not available")

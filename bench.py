@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--full]
 
-  (no --config)         cfg 2 as the headline `value`; on one GPU also `other_configs`: cfg 1 / 5 / 3 / 4, each as
-                        `python bench.py --config N` in a process of its own (shorter timed regions), summarised into the ONE line
+  (no --config)         cfg 2 as the headline `value`
+  --full                everything else the benchmark measures or checks: the config's side legs (below: end_to_end, serving,
+                        cpu_baseline, sustained, the single-flight calls behind kernel_ms / roofline / int_mac, the identity and
+                        exchange checks) and, without --config, `other_configs`: on one GPU cfg 1 / 5 / 3 / 4, each as
+                        `python bench.py --config N --full` in a process of its own (shorter timed regions), summarised into the ONE
+                        line; on N GPUs cfg 4 / 5 in the same process group.  Without --full a run sets up, warms up, times its steps,
+                        writes --dump-outputs and prints its line: nothing else
   --config 1            configs[0]: 4-replica clique, 100 RSA-2048 signed writes on the CPU path (the C restatement; plumbing, no GPU number)
   --config 2            configs[1]: 64-replica quorum, 10k RSA-2048 signed writes per GPU, batched verify; beside the resident
                         headline: `end_to_end` (the same batch handed over in pageable host memory: pipelined copy + verify, alone and
@@ -80,9 +85,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 200 for cfg 2 -- 0.6 s of timed region, long past the "
                     "fill and drain of the batches in flight --, 10 for the other configs)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--config", type=int, default=None, choices=(1, 2, 3, 4, 5), help="default: cfg 2 as the headline and, on one GPU, "
-                    "cfg 1 / 3 / 4 / 5 behind it as `other_configs`; --config N runs that config alone with its full line")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run: the cfg-2 line only")
+    ap.add_argument("--config", type=int, default=None, choices=(1, 2, 3, 4, 5), help="default: cfg 2 as the headline and, with --full, "
+                    "cfg 1 / 3 / 4 / 5 behind it as `other_configs`; --config N runs that config alone (its full line with --full)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything, not only the headline: the config's side legs "
+                    "and, without --config, the other configs behind the headline (the --no-* options below leave parts of it out)")
+    ap.add_argument("--no-other-configs", action="store_true", help="default run with --full: the cfg-2 line only")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of CPU work the cpu_baseline leg may sweep thread counts for")
     ap.add_argument("--items", type=int, default=0, help="cfg 2: signed writes per GPU and step (default 10000); cfg 3: variables "
                     "(default 10000, ~10 replies each); cfg 4: writes of the whole storm (default 1000000); cfg 5: operations per scheme (10000)")
@@ -111,8 +118,9 @@ def parse_args(argv=None):
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="cfg 2: after the timed steps, write what the last timed step "
                     "returned to its caller (error code, exit count and verdict bits per write, the gathered verdict bitmap) as DIR/<name>.npy in "
                     "float32, %d MB at most in all, so that two builds can be compared output for output" % (DUMP_MAX_BYTES >> 20))
-    ap.add_argument("--full-json", default=None, help="where the FULL record goes (sweeps, per-thread serving runs, timelines, notes, commands, "
-                    "every other config's record): default bench_full.json next to bench.py (bench_full_cfgN.json with --config N).  stdout "
+    ap.add_argument("--full-json", default=None, help="where the FULL record of a --full run goes (sweeps, per-thread serving runs, timelines, "
+                    "notes, commands, every other config's record): default bench_full.json next to bench.py (bench_full_cfgN.json with "
+                    "--config N); a run without --full writes one only here, if given.  stdout "
                     "carries ONE line of at most %d bytes -- the contract's keys, roofline, cpu_baseline, int_mac and a per-config summary" % LINE_MAX)
     args = ap.parse_args(argv)
     if args.dump_outputs and args.config not in (None, 2):
@@ -763,24 +771,24 @@ def bench_cfg2(args, D):
         e, nv, vd, bits = V.outs[k]
         dump_outputs(args.dump_outputs, {"err": e.cpu().numpy(), "n_verified": nv.cpu().numpy(), "verdict": vd.cpu().numpy(),
                                          "verdict_bitmap": bits.cpu().numpy()})
-    sclk = V.ctxs[0].last_sclk_mhz()
-    timed_rsa, timed_total, timed_hash = list(V.rsa_ms), list(V.total_ms), list(V.hash_ms)
-    iso = []
-    for _ in range(3):           # phase breakdown of an isolated call: non-overlapped calls on one context
-        V.submit(0); V.complete(0)
-        iso.append(dict(V.last_tm))
+    if args.full:
+        sclk = V.ctxs[0].last_sclk_mhz()
+        timed_rsa, timed_total, timed_hash = list(V.rsa_ms), list(V.total_ms), list(V.hash_ms)
+        iso = []
+        for _ in range(3):           # phase breakdown of an isolated call: non-overlapped calls on one context
+            V.submit(0); V.complete(0)
+            iso.append(dict(V.last_tm))
+    # context 0's last call (an isolated one with --full, a timed step without) verified the same resident batch as every step
     err, nver, bits = V.results(0)
-    gather_ok = V.check_gather(err, bits)
     counters = V.ctxs[0].last_counters()
     st_all, st_item = V.ctxs[0].last_statuses()
     ref_ops = reference_pubkey_ops(st_all, st_item, err, nver, items)
     total_sigs, total_items, total_ref_ops, total_done_ops = D.sum_ints([n_sigs, items, ref_ops, int(counters["pubkey_ops"])])
     ms_step = elapsed / args.steps * 1e3
-    sustained = soak(D, V.run, args.soak_seconds, ms_step, total_ref_ops)
+    if args.full:
+        gather_ok = V.check_gather(err, bits)
+        sustained = soak(D, V.run, args.soak_seconds, ms_step, total_ref_ops)
     if D.rank == 0:
-        rsa_ms = float(np.mean(timed_rsa))
-        iso_rsa = float(np.mean([t["rsa"] for t in iso]))
-        alg_bytes = int(z["to"][-1]) + ref_ops * RSA_BYTES + (items + 7) // 8      # SURVEY.md 8(d): payload once + 291 B per verify + 1 bit
         out = base_line(args, D, "pgp_rsa2048_signature_verifies_per_sec", "verifies/s", total_ref_ops * args.steps / elapsed, elapsed, "u32",
                         "%d-replica quorum, %d RSA-2048 signed writes per GPU (cfg2 of BASELINE.json), %d signature packets per GPU, "
                         "1.0%% corrupt / 0.5%% unknown issuer / 0.5%% duplicate / 1.0%% one-short" % (n, items, n_sigs),
@@ -796,11 +804,19 @@ def bench_cfg2(args, D):
             "pubkey_ops_performed_per_sec": total_done_ops * args.steps / elapsed,
             "packets_per_sec": total_sigs * args.steps / elapsed,
             "quorum_verdicts_per_sec": total_items * args.steps / elapsed,
-            "sufficient_fraction": float((err == 0).mean()),
-            "verdicts_match_construction": bool(((err == 0) == want_ok).all()),
-            "allgather": {"calls_in_timed_region": args.steps, "bytes_per_rank": (items + 7) // 8, "rows_consistent": gather_ok,
+            "allgather": {"calls_in_timed_region": args.steps, "bytes_per_rank": (items + 7) // 8,
                           "via": "bftkv_gpu_allgather_errs_dev (library RCCL, verifier stream)" if D.exchange == "library" else
                                  "torch.distributed.all_gather_into_tensor (FALLBACK: the library's communicator could not be set up; host-synchronised per step)"},
+            "corpus_build_s": t_corpus,
+        })
+    if args.full and D.rank == 0:
+        rsa_ms = float(np.mean(timed_rsa))
+        iso_rsa = float(np.mean([t["rsa"] for t in iso]))
+        alg_bytes = int(z["to"][-1]) + ref_ops * RSA_BYTES + (items + 7) // 8      # SURVEY.md 8(d): payload once + 291 B per verify + 1 bit
+        out["allgather"]["rows_consistent"] = gather_ok
+        out.update({
+            "sufficient_fraction": float((err == 0).mean()),
+            "verdicts_match_construction": bool(((err == 0) == want_ok).all()),
             "kernel_ms": {"k_rsa_modexp": rsa_ms, "k_rsa_modexp_min_max": [float(np.min(timed_rsa)), float(np.max(timed_rsa))],
                           "hash_stream": float(np.mean(timed_hash)), "step_device_span": float(np.mean(timed_total)),
                           "step_over_modexp": ms_step / iso_rsa if iso_rsa else None,
@@ -816,7 +832,6 @@ def bench_cfg2(args, D):
                                  in_flight_launch_ms=rsa_ms, launch_ms_basis="single_flight"),
             "int_mac": int_mac_block(counters["pubkey_ops"] * MACS_PER_RSA_VERIFY, ms_step, rsa_ms, iso_rsa, sclk, V.n_ctx),
             "sustained": sustained,
-            "corpus_build_s": t_corpus,
         })
         if D.world == 1 and not args.no_end_to_end:
             # the same batch handed over in HOST buffers (what a cgo caller does): H2D copy + pipeline + D2H of the verdicts.
@@ -1044,28 +1059,24 @@ def bench_cfg3(args, D):
 
     run(V.n_ctx)                 # one untimed step per verifier context: its arena is allocated at its first call
     elapsed = timed_region(D, run, args.steps, args.warmup, V.reset_timing)
-    sclk = V.ctxs[0].last_sclk_mhz()
-    timed_rsa, timed_dsa, timed_hash, timed_total = list(V.rsa_ms), list(V.dsa_ms), list(V.hash_ms), list(V.total_ms)
-    iso = []
-    for _ in range(3):           # single-flight: non-overlapped calls on one context (the in-flight spans above overlap each other)
-        V.submit(0); V.complete(0)
-        iso.append(dict(V.last_tm))
+    if args.full:
+        sclk = V.ctxs[0].last_sclk_mhz()
+        timed_rsa, timed_dsa, timed_hash, timed_total = list(V.rsa_ms), list(V.dsa_ms), list(V.hash_ms), list(V.total_ms)
+        iso = []
+        for _ in range(3):           # single-flight: non-overlapped calls on one context (the in-flight spans above overlap each other)
+            V.submit(0); V.complete(0)
+            iso.append(dict(V.last_tm))
     err, nver, bits = V.results(0)
-    gather_ok = V.check_gather(err, bits)
     counters = V.ctxs[0].last_counters()
     n_dsa_ops = int(counters["dsa_ops"])
     st_all, st_item = V.ctxs[0].last_statuses()
     ref_ops = reference_pubkey_ops(st_all, st_item, err, nver, n_replies)
     tot_sigs, tot_replies, tot_vars, tot_ref_ops, tot_done_ops = D.sum_ints([rc.n_sigs, n_replies, n_vars, ref_ops, int(counters["pubkey_ops"])])
     win = winners[0]
-    sustained = soak(D, run, args.soak_seconds, elapsed / args.steps * 1e3, tot_ref_ops)
+    if args.full:
+        gather_ok = V.check_gather(err, bits)
+        sustained = soak(D, run, args.soak_seconds, elapsed / args.steps * 1e3, tot_ref_ops)
     if D.rank == 0:
-        rsa_ms, dsa_ms = float(np.mean(timed_rsa)), float(np.mean(timed_dsa))                 # spans with V.n_ctx steps in flight
-        iso_rsa, iso_dsa = float(np.mean([t["rsa"] for t in iso])), float(np.mean([t["dsa"] for t in iso]))
-        n_rsa_ops = int(counters["pubkey_ops"]) - n_dsa_ops
-        dsa_bits = V.ctxs[0].dsa_window_bits()        # the width the tables were built at decides the MAC count of a verification
-        dom = "k_dsa_modexp" if iso_dsa >= iso_rsa else "k_rsa_modexp"
-        alg_bytes = int(rc.tbss_off[-1]) + n_rsa_ops * RSA_BYTES + n_dsa_ops * DSA_BYTES + (n_replies + 7) // 8
         out = base_line(args, D, "pgp_mixed_rsa_dsa_signature_verifies_per_sec", "verifies/s", tot_ref_ops * args.steps / elapsed, elapsed, "u32",
                         "%d-replica quorum (half RSA-2048, half DSA-2048/256), %d signed read replies <x,v,t,sig,ss> over %d variables per GPU "
                         "(cfg3 of BASELINE.json: %d distinct stored packets, 2 timestamps per variable, 1%% of the variables with a conflicting "
@@ -1073,6 +1084,7 @@ def bench_cfg3(args, D):
                         "quorum" % (n, n_replies, n_vars, rc.writes.n_items, rc.n_sigs, ns),
                         {"replicas": n, "replies_per_gpu": n_replies, "variables_per_gpu": n_vars, "sigs_per_gpu": rc.n_sigs,
                          "batches_in_flight": V.n_ctx, "parallelism": "shard-by-variable x%d, RCCL all-gather of reply-verdict bitmaps" % D.world})
+        n_rsa_ops = int(counters["pubkey_ops"]) - n_dsa_ops
         out.update({
             "value_counts": "RSA-2048 / DSA-2048 public-key verifications on the REFERENCE's operation count (packets "
                             "PGPCollectiveSignature.Verify examines before IsSufficient stops it that reach the public-key operation)",
@@ -1080,9 +1092,19 @@ def bench_cfg3(args, D):
             "pubkey_ops_performed_per_sec": tot_done_ops * args.steps / elapsed, "packets_per_sec": tot_sigs * args.steps / elapsed,
             "reply_verdicts_per_sec": tot_replies * args.steps / elapsed, "read_verdicts_per_sec": tot_vars * args.steps / elapsed,
             "pubkey_ops_per_step_per_gpu": {"rsa": n_rsa_ops, "dsa": n_dsa_ops},
+            "allgather": {"calls_in_timed_region": args.steps, "bytes_per_rank": (n_replies + 7) // 8},
+            "corpus_build_s": t_corpus,
+        })
+    if args.full and D.rank == 0:
+        rsa_ms, dsa_ms = float(np.mean(timed_rsa)), float(np.mean(timed_dsa))                 # spans with V.n_ctx steps in flight
+        iso_rsa, iso_dsa = float(np.mean([t["rsa"] for t in iso])), float(np.mean([t["dsa"] for t in iso]))
+        dsa_bits = V.ctxs[0].dsa_window_bits()        # the width the tables were built at decides the MAC count of a verification
+        dom = "k_dsa_modexp" if iso_dsa >= iso_rsa else "k_rsa_modexp"
+        alg_bytes = int(rc.tbss_off[-1]) + n_rsa_ops * RSA_BYTES + n_dsa_ops * DSA_BYTES + (n_replies + 7) // 8
+        out["allgather"]["rows_consistent"] = gather_ok
+        out.update({
             "sustained": sustained,
             "reads_answered_fraction": float(np.mean(win >= 0)), "replies_accepted_fraction": float((err == 0).mean()),
-            "allgather": {"calls_in_timed_region": args.steps, "bytes_per_rank": (n_replies + 7) // 8, "rows_consistent": gather_ok},
             "kernel_ms": {"k_rsa_modexp": rsa_ms, "k_dsa_mul+k_dsa_modexp": dsa_ms, "hash_stream": float(np.mean(timed_hash)),
                           "step_device_span": float(np.mean(timed_total)),
                           "measured": "HIP events of the %d timed steps, %d in flight: SPANS that overlap the neighbouring steps' kernels, not "
@@ -1103,7 +1125,6 @@ def bench_cfg3(args, D):
                            "note": "width chosen by the library for this keyring and the free HBM (bftkv_gpu_dsa_window_bits: the widest of 18 / 16 / "
                                    "15 / 14 / 13 / 12 / 10 / 8 bits whose tables fit); bftkv_gpu_set_dsa_table_budget bounds it (32 keys: 8 GB -> 14 "
                                    "bits, 24 GB -> 16); gb_pinned = the tables of the ring's keys, gb_allocated = the arena with its growth margin"},
-            "corpus_build_s": t_corpus,
         })
         if D.world == 1 and not args.no_cpu_baseline:
             # the CPU path on the DISTINCT stored packets (a reply is a byte-identical copy of one of them), mapped to the replies
@@ -1231,9 +1252,10 @@ def bench_cfg4(args, D):
     V.run(n_fl)                  # one untimed call per verifier context: its arena is allocated at its first call
 
     elapsed = timed_region(D, run, args.steps, args.warmup, V.reset_timing)
-    sclk = V.ctxs[0].last_sclk_mhz()
     err, nver, bits = V.results(0)
-    gather_ok = V.check_gather(err, bits)
+    if args.full:
+        sclk = V.ctxs[0].last_sclk_mhz()
+        gather_ok = V.check_gather(err, bits)
     counters = V.ctxs[0].last_counters()
     n_sigs_call = n_sigs_base * tiles
     st_all, st_item = V.ctxs[0].last_statuses()
@@ -1242,9 +1264,6 @@ def bench_cfg4(args, D):
     tot_sigs, tot_writes, tot_ref_ops, tot_done_ops = D.sum_ints([n_sigs_call * calls, chunk * calls, ref_ops_call * calls,
                                                                   int(counters["pubkey_ops"]) * calls])
     if D.rank == 0:
-        rsa_ms, hash_ms = float(np.mean(V.rsa_ms)), float(np.mean(V.hash_ms))
-        alg_bytes = tiles * int(z["to"][-1]) + ref_ops_call * RSA_BYTES + (chunk + 7) // 8
-        want_ok = np.tile(z["expected_valid"] >= cl.suff, tiles)
         out = base_line(args, D, "pgp_rsa2048_signature_verifies_per_sec", "verifies/s", tot_ref_ops * args.steps / elapsed, elapsed, "u32",
                         "%d-replica quorum, write storm of %d signed writes per step over %d GPU(s) (cfg4 of BASELINE.json): each rank verifies "
                         "its %d writes as %d call(s) over a resident batch of %d writes = %d tiles of %d distinctly signed writes "
@@ -1262,14 +1281,21 @@ def bench_cfg4(args, D):
             "pubkey_ops_performed_per_sec": tot_done_ops * args.steps / elapsed, "packets_per_sec": tot_sigs * args.steps / elapsed,
             "quorum_verdicts_per_sec": tot_writes * args.steps / elapsed,
             "pubkey_ops_per_call": int(counters["pubkey_ops"]),
+            "allgather": {"calls_in_timed_region": args.steps * calls, "bytes_per_rank": (chunk + 7) // 8},
+            "corpus_build_s": t_corpus,
+        })
+    if args.full and D.rank == 0:
+        rsa_ms, hash_ms = float(np.mean(V.rsa_ms)), float(np.mean(V.hash_ms))
+        alg_bytes = tiles * int(z["to"][-1]) + ref_ops_call * RSA_BYTES + (chunk + 7) // 8
+        want_ok = np.tile(z["expected_valid"] >= cl.suff, tiles)
+        out["allgather"]["rows_consistent"] = gather_ok
+        out.update({
             "sufficient_fraction": float((err == 0).mean()),
             "verdicts_match_construction": bool(((err == 0) == want_ok).all()),
-            "allgather": {"calls_in_timed_region": args.steps * calls, "bytes_per_rank": (chunk + 7) // 8, "rows_consistent": gather_ok},
             "kernel_ms": {"k_rsa_modexp": rsa_ms, "hash_stream": hash_ms, "call_device_span": float(np.mean(V.total_ms)),
                           "measured": "HIP events of the %d timed calls" % len(V.rsa_ms), "last_call": V.last_tm},
             "roofline": roofline(4, "k_rsa_modexp", alg_bytes, rsa_ms, "integer-VALU bound; see int_mac"),
             "int_mac": int_mac_block(counters["pubkey_ops"] * MACS_PER_RSA_VERIFY * calls, elapsed / args.steps * 1e3, rsa_ms * calls, None, sclk, V.n_ctx),
-            "corpus_build_s": t_corpus,
         })
         if D.world == 1 and not args.no_cpu_baseline:
             cerr, cnver, ops, best, nt, st1 = cpu_collective(cl, z["tb"], z["to"], z["sb"], z["so"], budget_s=args.cpu_budget)
@@ -1432,28 +1458,24 @@ def bench_cfg5(args, D):
 
     run(n_ctx)                   # one untimed step per context (scratch and modulus tables are allocated at the first call)
     elapsed = timed_region(D, run, args.steps, args.warmup, lambda: spans.clear())
-    res = {k: o[k].cpu().numpy() for k in o}
-    for other in outs[1:]:
-        for k in o:
-            assert torch.equal(other[k], o[k]), "contexts disagree on " + k
     tot_ops = D.sum_ints([3 * N])[0]
-    sustained = soak(D, run, args.soak_seconds, elapsed / args.steps * 1e3, tot_ops)
-    # ONE batch at a time -- the workload BASELINE configs[4] names, without the steps in flight that the headline needs: each step
-    # is waited for before the next is issued
-    n_single = 6
-    spans_timed = [list(x) for x in spans]
-    spans.clear()
-    t0 = time.perf_counter()
-    for _ in range(n_single):
-        run(1)
-    single_ms = D.max_float(time.perf_counter() - t0) / n_single * 1e3
-    single_r_ms = float(np.mean(np.array(spans), axis=0)[3])
+    if args.full:
+        res = {k: o[k].cpu().numpy() for k in o}
+        for other in outs[1:]:
+            for k in o:
+                assert torch.equal(other[k], o[k]), "contexts disagree on " + k
+        sustained = soak(D, run, args.soak_seconds, elapsed / args.steps * 1e3, tot_ops)
+        # ONE batch at a time -- the workload BASELINE configs[4] names, without the steps in flight that the headline needs: each step
+        # is waited for before the next is issued
+        n_single = 6
+        spans_timed = [list(x) for x in spans]
+        spans.clear()
+        t0 = time.perf_counter()
+        for _ in range(n_single):
+            run(1)
+        single_ms = D.max_float(time.perf_counter() - t0) / n_single * 1e3
+        single_r_ms = float(np.mean(np.array(spans), axis=0)[3])
     if D.rank == 0:
-        sp = np.mean(np.array(spans_timed), axis=0)
-        names = ["rsa_combine_n10", "sss_calculate_secret_k%d_2048" % K_SSS, "dsa_calculate_s_2t%d_q256" % K_DSA, "dsa_calculate_r_2t%d_2048_256" % K_DSA]
-        # dominant: CalculateR.  Algorithmic bytes per op (SURVEY.md 8(d)): 2t x (|p| + |q|) in, |q| out
-        alg_r = N * (K_DSA * (256 + 32) + 32)
-        alg_all = N * ((10 + 1) * 256 + (K_SSS + 1) * 256 + K_SSS * 4 + (K_DSA + 1) * 32 + K_DSA * 4 + K_DSA * (256 + 32) + K_DSA * 4 + 32)
         out = base_line(args, D, "threshold_share_combine_ops_per_sec", "ops/s", tot_ops * args.steps / elapsed, elapsed, "u32",
                         "threshold share-combine (cfg5 of BASELINE.json): per step %d operations of each scheme over %d GPU(s) -- RSA calculateSignature "
                         "(product of 10 partial signatures mod the 2048-bit N of rsa/test.pkcs8), SSS calculateSecret (k=7 of n=10, mod the 2048-bit "
@@ -1466,6 +1488,13 @@ def bench_cfg5(args, D):
                         {"ops_per_scheme": n_total, "ops_per_scheme_per_gpu": N, "schemes": 3, "steps_in_flight": n_ctx,
                          "parallelism": "shard-by-operation x%d, no exchange step (results go back to the one client that asked)" % D.world},
                         scaling="strong")
+        out["corpus_build_s"] = t_corpus
+    if args.full and D.rank == 0:
+        sp = np.mean(np.array(spans_timed), axis=0)
+        names = ["rsa_combine_n10", "sss_calculate_secret_k%d_2048" % K_SSS, "dsa_calculate_s_2t%d_q256" % K_DSA, "dsa_calculate_r_2t%d_2048_256" % K_DSA]
+        # dominant: CalculateR.  Algorithmic bytes per op (SURVEY.md 8(d)): 2t x (|p| + |q|) in, |q| out
+        alg_r = N * (K_DSA * (256 + 32) + 32)
+        alg_all = N * ((10 + 1) * 256 + (K_SSS + 1) * 256 + K_SSS * 4 + (K_DSA + 1) * 32 + K_DSA * 4 + K_DSA * (256 + 32) + K_DSA * 4 + 32)
         out.update({
             "per_scheme_ops_per_sec_per_gpu": {names[i]: N / (sp[i] * 1e-3) for i in range(4)},
             "kernel_ms": {names[i]: float(sp[i]) for i in range(4)},
@@ -1480,7 +1509,6 @@ def bench_cfg5(args, D):
                               "power; 4-bit windows over the 64 windows of a 256-bit q: 715 general products and 512 squarings)" % macs_per_calculate_r(K_DSA, 64),
             "algorithmic_bytes_per_step": alg_all,
             "sustained": sustained,
-            "corpus_build_s": t_corpus,
         })
         sf = int_mac(N * macs_per_calculate_r(K_DSA, 64), single_ms)
         out["single_flight"] = {"what": "the same step with ONE batch of %d operations per scheme on the device at a time (no steps in flight): "
@@ -1561,17 +1589,18 @@ def bench_cfg1(args, D):
         cerr, cnver, ops = co.collective_verify(z["tb"], z["to"], z["sb"], z["so"], n_threads=1)
         reps.append(time.perf_counter() - t0)
     t1 = min(reps)
-    cores = effective_cores()
-    t0 = time.perf_counter()
-    co.collective_verify(z["tb"], z["to"], z["sb"], z["so"], n_threads=cores)
-    tn = time.perf_counter() - t0
     out = {"metric": "pgp_rsa2048_signature_verifies_per_sec", "value": ops / t1, "unit": "verifies/s", "device": "cpu",
            "workload": "4-replica wotqs clique, %d RSA-2048 signed writes (cfg1 of BASELINE.json), %d signature packets, %d public-key ops after "
                        "the early exit at suff=%d" % (items, int(z["n_sigs"]), ops, cl.suff),
            "ms_per_step": t1 * 1e3, "writes_per_sec": items / t1, "threads": 1,
-           "all_cores": {"threads": cores, "verifies_per_sec": ops / tn, "writes_per_sec": items / tn},
            "kind": "port", "what": "oracle/c/oracle.c (C on OpenSSL libcrypto; the Go reference cannot be built here), best of 5 passes"}
-    if not D.dry:
+    if args.full:
+        cores = effective_cores()
+        t0 = time.perf_counter()
+        co.collective_verify(z["tb"], z["to"], z["sb"], z["so"], n_threads=cores)
+        tn = time.perf_counter() - t0
+        out["all_cores"] = {"threads": cores, "verifies_per_sec": ops / tn, "writes_per_sec": items / tn}
+    if args.full and not D.dry:
         from bftkv_amd import Context
         from tests import helpers as H
         ctx = Context(D.local_rank)
@@ -1618,8 +1647,8 @@ def summarize(out):
 
 
 def other_configs(args, D):
-    """cfg 1, 3, 4, 5 at full size behind the cfg-2 headline of a default run: each in a FRESH process running exactly
-    `python bench.py --config N` (shorter timed regions, no soak, bounded CPU legs).  A process of its own because that is what the
+    """cfg 1, 3, 4, 5 at full size behind the cfg-2 headline of a default --full run: each in a FRESH process running exactly
+    `python bench.py --config N --full` (shorter timed regions, no soak, bounded CPU legs).  A process of its own because that is what the
     per-config numbers of DESIGN.md are (cfg 5 read 9.2 ms per step in the process that had just run cfg 2 -- its streams land on
     the runtime's hardware queues differently -- and 7.6 alone), and because a failure or a hang of one config is then recorded
     in its entry and can never take the headline down."""
@@ -1633,7 +1662,7 @@ def other_configs(args, D):
     full = {}
     for cfg, extra in plan:
         # (cfg 5 keeps its `serving` leg: one share-combine per call through the micro-batcher, ~20 s)
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cfg), "--gpus", "1", "--soak-seconds", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cfg), "--full", "--gpus", "1", "--soak-seconds", "0",
                "--cpu-budget", str(min(args.cpu_budget, 10.0))] + ([] if cfg == 5 else ["--no-serving"]) + extra + \
               (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
         t0 = time.time()
@@ -1797,6 +1826,8 @@ def compact_line(out, full_path=None):
     if ag:
         line["exchange"] = {"rows_consistent": ag.get("rows_consistent"), "bytes_per_rank": ag.get("bytes_per_rank"),
                             "via": "library RCCL on the verifier's stream" if str(ag.get("via", "")).startswith("bftkv_gpu") else "torch.distributed (fallback)"}
+        if "rows_consistent" not in ag:         # (checked by --full runs only)
+            del line["exchange"]["rows_consistent"]
     rf = out.get("roofline")
     if rf:
         line["roofline"] = {k: rf.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "launch_ms_basis",
@@ -1878,7 +1909,7 @@ def compact_line(out, full_path=None):
 
 
 def multi_rank_extras(args, D, emit):
-    """N > 1, default run: BASELINE's actual multi-GPU configs behind the cfg-2 headline, IN this process group -- cfg 4 (the
+    """N > 1, default --full run: BASELINE's actual multi-GPU configs behind the cfg-2 headline, IN this process group -- cfg 4 (the
     1 M-write storm split over the ranks, one RCCL all-gather of verdict bitmaps per call; strong scaling) and cfg 5 (10 k combines
     per scheme sharded by operation, no exchange; strong scaling), with short timed regions.  (On one GPU `other_configs` runs every
     config in a process of its own; ranks of a torchrun group cannot spawn a second group, so here they run in line: cfg 5 then sees
@@ -1901,7 +1932,7 @@ def multi_rank_extras(args, D, emit):
     try:
         for cfg, extra in plan:
             key = "cfg%d" % cfg
-            argv = ["--config", str(cfg), "--gpus", str(D.world), "--soak-seconds", "0", "--no-serving", "--no-cpu-baseline"] + extra
+            argv = ["--config", str(cfg), "--full", "--gpus", str(D.world), "--soak-seconds", "0", "--no-serving", "--no-cpu-baseline"] + extra
             if D.dry:
                 argv += ["--dry-run"] + (["--items", str(args.items * 64)] if cfg == 4 and args.items else []) + \
                         (["--distinct", "8", "--chunk", "64"] if cfg == 4 and args.items else [])
@@ -1941,8 +1972,8 @@ def main():
     D = Dist(args)
     try:
         default_run = args.config is None
-        everything = (default_run and D.world == 1 and not args.dry_run and not args.no_other_configs and
-                      os.environ.get("BFTKV_BENCH_EXTRAS_IN_PROCESS") != "1")
+        with_others = default_run and args.full and not args.no_other_configs
+        everything = with_others and D.world == 1 and not args.dry_run and os.environ.get("BFTKV_BENCH_EXTRAS_IN_PROCESS") != "1"
         if args.config is None:
             args.config = 2
         out = {1: bench_cfg1, 2: bench_cfg2, 3: bench_cfg3, 4: bench_cfg4, 5: bench_cfg5}[args.config](args, D)
@@ -1960,22 +1991,26 @@ def main():
                     out["summary"] = line_summary(out)
                 except Exception as e:                    # noqa: BLE001 -- a digest must never take the record down
                     out["summary"] = {"error": repr(e)[:200]}
-                # the FULL record: a side file and stderr; stdout gets the short line (LINE_MAX bytes at most)
-                path = args.full_json or os.path.join(ROOT, "bench_full.json" if default_run else "bench_full_cfg%d.json" % args.config)
-                full = dict(out)
-                if OTHER_FULL:
-                    full["other_configs_full"] = dict(OTHER_FULL)
-                try:
-                    with open(path, "w") as fh:
-                        json.dump(full, fh)
-                        fh.write("\n")
-                except OSError as e:
-                    sys.stderr.write("bench.py: full record not written to %s: %s\n" % (path, e))
-                    path = None
-                # (on ONE stderr line that does not start with a brace: a reader that takes the last line beginning with "{" of whatever
-                # it captured must find the stdout line, not this one)
-                sys.stderr.write("bench.py: full record%s: %s\n" % (" (%s)" % path if path else "", json.dumps(out)))
-                sys.stderr.flush()
+                # the FULL record of a --full run: a side file and stderr; stdout gets the short line (LINE_MAX bytes at most)
+                path = args.full_json
+                if args.full and not path:
+                    path = os.path.join(ROOT, "bench_full.json" if default_run else "bench_full_cfg%d.json" % args.config)
+                if path:
+                    full = dict(out)
+                    if OTHER_FULL:
+                        full["other_configs_full"] = dict(OTHER_FULL)
+                    try:
+                        with open(path, "w") as fh:
+                            json.dump(full, fh)
+                            fh.write("\n")
+                    except OSError as e:
+                        sys.stderr.write("bench.py: full record not written to %s: %s\n" % (path, e))
+                        path = None
+                if args.full:
+                    # (on ONE stderr line that does not start with a brace: a reader that takes the last line beginning with "{" of
+                    # whatever it captured must find the stdout line, not this one)
+                    sys.stderr.write("bench.py: full record%s: %s\n" % (" (%s)" % path if path else "", json.dumps(out)))
+                    sys.stderr.flush()
                 try:
                     line = json.dumps(compact_line(out, path))
                 except Exception as e:                    # noqa: BLE001 -- the contract's keys at the very least
@@ -1995,7 +2030,7 @@ def main():
         rehearse = os.environ.get("BFTKV_BENCH_EXTRAS_IN_PROCESS") == "1" and not args.dry_run
         if rehearse and out is not None:
             out.pop("other_configs", None)
-        if default_run and (D.world > 1 or rehearse) and not args.no_other_configs:
+        if with_others and (D.world > 1 or rehearse):
             extra = multi_rank_extras(args, D, emit)
             if out is not None:
                 out["other_configs"] = extra

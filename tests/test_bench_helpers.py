@@ -42,7 +42,7 @@ def test_cfg1_leg_times_the_c_restatement_on_the_reference_shape():
     """BASELINE.json configs[0]: 4 replicas, 100 RSA-2048 signed writes on the CPU path (dry: without the GPU identity call)."""
     class D:
         dry, rank, world, local_rank = True, 0, 1, 0
-    out = bench.bench_cfg1(bench.parse_args(["--config", "1", "--dry-run"]), D)
+    out = bench.bench_cfg1(bench.parse_args(["--config", "1", "--full", "--dry-run"]), D)
     assert out["device"] == "cpu" and out["unit"] == "verifies/s" and out["value"] > 0 and out["threads"] == 1
     assert "4-replica" in out["workload"] and "100 RSA-2048" in out["workload"] and out["all_cores"]["threads"] == bench.effective_cores()
 

@@ -35,6 +35,7 @@ def _run(extra, env=None):
 def test_gpus_flag_spawns_the_ranks():
     r = _run(["--gpus", "2"])
     assert r["n_gpus"] == 2 and r["world_size"] == 2
+    assert "other_configs" not in r                       # a run without --full is the headline alone
     assert r["allgathers_in_step_loop"] == 3 + 2          # one exchange per step, warm-up included
     assert r["gather_rows"] == 2 and r["own_row_matches"]
     assert r["gathered_ok"] == r["sum_of_rank_ok"] and 0 < r["gathered_ok"] < 2 * 24
@@ -129,9 +130,9 @@ def test_cfg3_ranks_with_different_reply_counts_share_one_bitmap_width(world):
 
 @pytest.mark.parametrize("world", (2, 8))
 def test_default_line_of_a_multi_rank_run_carries_cfg4_and_cfg5(world):
-    """`bench.py --gpus N` (N > 1) prints ONE line: cfg 2's, with the storm (cfg 4) and the share combine (cfg 5) behind it as
+    """`bench.py --gpus N --full` (N > 1) prints ONE line: cfg 2's, with the storm (cfg 4) and the share combine (cfg 5) behind it as
     `other_configs`, run in the same process group."""
-    r = _run(["--gpus", str(world)])
+    r = _run(["--gpus", str(world), "--full"])
     assert r["world_size"] == world and r["config"] == 2 and r["gather_rows"] == world
     oc = r["other_configs"]
     assert set(oc) == {"cfg4", "cfg5"} and "error" not in oc["cfg4"] and "error" not in oc["cfg5"]

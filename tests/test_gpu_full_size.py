@@ -1,6 +1,6 @@
 """-m gpu: BASELINE.json configs[2], [3], [4] at FULL size on the device, checked against the CPU restatements.
 
-These run the very functions `python bench.py --config 3|4|5` runs (one timed step, no soak) and assert what those lines only
+These run the very functions `python bench.py --config 3|4|5 --full` runs (one timed step, no soak) and assert what those lines only
 report: every reply verdict and exit count of cfg 3 against oracle/c/oracle.c and every read answer against
 oracle.collective.max_timestamped_value; one 125,000-write call of cfg 4 (26.6 M signature packets, 256 replicas) against the C
 restatement on its distinct writes and against the corpus' construction; 10,000 operations of every threshold scheme of cfg 5
@@ -21,7 +21,7 @@ def D(gpu_ctx):          # gpu_ctx first: torch's HIP runtime is loaded before t
 
 
 def _args(cfg, *extra):
-    return bench.parse_args(["--config", str(cfg), "--steps", "1", "--warmup", "0", "--soak-seconds", "0", "--cpu-budget", "8"] + list(extra))
+    return bench.parse_args(["--config", str(cfg), "--full", "--steps", "1", "--warmup", "0", "--soak-seconds", "0", "--cpu-budget", "8"] + list(extra))
 
 
 def test_cfg3_full_size_reply_verdicts_and_read_answers(D):

@@ -7,7 +7,7 @@ for w in "$@"; do
   if [ "$w" = auto ]; then unset BFTKV_DSA_WBITS; else export BFTKV_DSA_WBITS=$w; fi
   extra="--no-cpu-baseline"
   [ "$w" = auto ] && extra="--cpu-budget 20"
-  python bench.py --config 3 --replicas $n --items $items --steps 6 --warmup 2 --soak-seconds 0 --corpus-cache /tmp/cc/c3 $extra \
+  python bench.py --config 3 --full --replicas $n --items $items --steps 6 --warmup 2 --soak-seconds 0 --corpus-cache /tmp/cc/c3 $extra \
       > gpurun_out/r5_cfg3_n${n}_w${w}.json 2> gpurun_out/r5_cfg3_n${n}_w${w}.err || tail -5 gpurun_out/r5_cfg3_n${n}_w${w}.err
   python - <<PY
 import json

@@ -9,7 +9,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -5 $OUT/pytest.log
 fi
 for cfg in ${CONFIGS-2 3 4 5}; do
-  timeout 900 python bench.py --config $cfg --steps ${STEPS:-5} --warmup 2 > $OUT/bench_cfg$cfg.json 2> $OUT/bench_cfg$cfg.err; echo "cfg$cfg rc=$?"
+  timeout 900 python bench.py --config $cfg --full --steps ${STEPS:-5} --warmup 2 > $OUT/bench_cfg$cfg.json 2> $OUT/bench_cfg$cfg.err; echo "cfg$cfg rc=$?"
   python - "$OUT/bench_cfg$cfg.json" <<'PY'
 import json, sys
 try:

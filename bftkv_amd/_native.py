@@ -47,6 +47,7 @@ EXPORTS = [
     "bftkv_gpu_collective_verify_small", "bftkv_gpu_signature_verify_small", "bftkv_gpu_set_hash_policy", "bftkv_gpu_signers_fenced",
     "bftkv_gpu_set_host_pipeline", "bftkv_gpu_batcher_cert_verify", "bftkv_gpu_host_pipeline_trace",
     "bftkv_gpu_batcher_cert_entity", "bftkv_gpu_set_lagrange_x_bound", "bftkv_gpu_batcher_modmul_product", "bftkv_gpu_batcher_lagrange_combine", "bftkv_gpu_batcher_dsa_calculate_r", "bftkv_gpu_batcher_modexp",
+    "bftkv_gpu_ecdsa_calculate_r", "bftkv_gpu_ecdsa_calculate_r_dev", "bftkv_gpu_batcher_ecdsa_calculate_r", "bftkv_gpu_ec_scalar_base_mult",
 ]
 
 _lib = None
@@ -133,6 +134,10 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_dsa_calculate_r_dev.argtypes = lib.bftkv_gpu_dsa_calculate_r.argtypes
     lib.bftkv_gpu_sss_distribute_dev.argtypes = lib.bftkv_gpu_sss_distribute.argtypes
     lib.bftkv_gpu_modinv_dev.argtypes = lib.bftkv_gpu_modinv.argtypes
+    lib.bftkv_gpu_ecdsa_calculate_r.argtypes = [vp, u32, u32, vp, u8p, u8p, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_ecdsa_calculate_r_dev.argtypes = lib.bftkv_gpu_ecdsa_calculate_r.argtypes
+    lib.bftkv_gpu_batcher_ecdsa_calculate_r.argtypes = [vp, u32, vp, u8p, u8p, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_ec_scalar_base_mult.argtypes = [vp, u32, u8p, u32, u8p, u32, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -548,6 +553,31 @@ class Context:
         return out
 
 
+    def ecdsa_calculate_r(self, xs, ri, vi, curve):
+        """ECDSA CalculateR (ecdsa.go:36-59): xs [n_ops][k] ints, ri [n_ops][k] Marshal bytes (1 + 2 fbytes each), vi [n_ops][k]
+        ints; curve: {p, n, b, gx, gy, bit_size} -> ([n_ops] ints, status)."""
+        cb, bits, f = _curve_bytes(curve)
+        n, k = len(xs), len(xs[0])
+        x = np.ascontiguousarray(np.array(xs, dtype=np.int32))
+        r = _u8(b"".join(bytes(v) for row in ri for v in row))
+        v = _ints_to_be([v for row in vi for v in row], f)
+        out = np.zeros((n, f), dtype=np.uint8)
+        st = np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_ecdsa_calculate_r(self.h, n, k, _ptr(x), _ptr(r), _ptr(v), _ptr(cb), bits, _ptr(out), _ptr(st)),
+                    "ecdsa_calculate_r")
+        return [int.from_bytes(out[i].tobytes(), "big") for i in range(n)], st[:n]
+
+    def ec_scalar_base_mult(self, scalars, curve):
+        """ECDSA CalculatePartialR (ecdsa.go:31-34): [n_ops] ints -> ([n_ops] Marshal bytes, status)."""
+        cb, bits, f = _curve_bytes(curve)
+        n = len(scalars)
+        sc = _ints_to_be(scalars, f)
+        out = np.zeros((n, 1 + 2 * f), dtype=np.uint8)
+        st = np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_ec_scalar_base_mult(self.h, n, _ptr(sc), f, _ptr(cb), bits, _ptr(out), _ptr(st)), "ec_scalar_base_mult")
+        return [out[i].tobytes() for i in range(n)], st[:n]
+
+
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
 
@@ -654,6 +684,15 @@ class Batcher:
         rc = self.lib.bftkv_gpu_batcher_dsa_calculate_r(self.h, len(xs), _ptr(x), _ptr(r), pbytes, _ptr(v), qbytes, _ptr(pb), _ptr(qb), _ptr(out), _ptr(st))
         return rc, int(st[0]), int.from_bytes(out.tobytes(), "big")
 
+    def ecdsa_calculate_r(self, xs, ri, vi, curve):
+        """ECDSA CalculateR (ecdsa.go:36-59) for one operation: ri [k] Marshal bytes, vi [k] ints -> (rc, status, r)."""
+        cb, bits, f = _curve_bytes(curve)
+        x = np.ascontiguousarray(np.array(xs, dtype=np.int32))
+        r, v = _u8(b"".join(bytes(p) for p in ri)), _ints_to_be(vi, f)
+        out, st = np.full(f, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_ecdsa_calculate_r(self.h, len(xs), _ptr(x), _ptr(r), _ptr(v), _ptr(cb), bits, _ptr(out), _ptr(st))
+        return rc, int(st[0]), int.from_bytes(out.tobytes(), "big")
+
     def modexp(self, base: int, exp: int, mod: int, nbytes: int = 256, exp_len: int = 32):
         """base^exp mod `mod` (CalculatePartialR dsa.go:27-31; the per-fragment power of rsa.go:161-171)."""
         b, e, m = _ints_to_be([base], nbytes), _ints_to_be([exp], exp_len), _ints_to_be([mod], nbytes)
@@ -667,6 +706,13 @@ class Batcher:
         ns = (C.c_uint64 * 8)()
         self.lib.bftkv_gpu_batcher_times(self.h, ns)
         return {"calls": st[0], "batches": st[1], "max_batch": st[2], "lanes": st[3], "cert_fast": ns[7]}
+
+
+def _curve_bytes(curve):
+    """{p, n, b, gx, gy, bit_size} -> (P || N || B || Gx || Gy as uint8, bit_size, fbytes)."""
+    bits = int(curve["bit_size"])
+    f = (bits + 7) // 8
+    return _ints_to_be([int(curve[key]) for key in ("p", "n", "b", "gx", "gy")], f).reshape(-1).copy(), bits, f
 
 
 def _ints_to_be(vals, nbytes: int) -> np.ndarray:

@@ -278,7 +278,7 @@ struct bftkv_gpu_batcher {
     int kind;                  // 0 collective verify, 1 signature verify, 2 transport message (tbs = the packet sequence),
                                // 3 Issuer + VerifyWithCertificate over a request certificate (cert / cert_len below),
                                // 4..7 ONE threshold share-combine operation (th_* below): 4 prod psig mod N, 5 sum l_j y_j mod m,
-                               // 6 CalculateR, 7 b^x mod n
+                               // 6 CalculateR, 7 b^x mod n, 8 ECDSA CalculateR
     int quorum;
     const uint8_t* tbs; uint64_t tbs_len;
     const uint8_t* sig; uint64_t sig_len;
@@ -459,9 +459,33 @@ struct bftkv_gpu_batcher {
   // kinds 4..7: the group's operations in ONE call of the batched entry point on the lane's context (threshold_capi.inc).  The
   // distinct moduli of the group go into the call's modulus table in BYTE ORDER, so that the same set of moduli -- a protocol
   // instance combines under the same few CA keys call after call -- finds its Montgomery tables in the context's cache.
+  // kind 8: ECDSA CalculateR.  A group's callers share one recognised curve (its bit size is part of the shape), which the
+  // call takes by value (th_mod = P || N || B || Gx || Gy, th_nbytes = fbytes, th_qbytes = bit size)
+  void run_ecdsa(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), k = r0.th_k, f = r0.th_nbytes;
+    const size_t rw = (size_t)k * (1 + 2 * f), vw = (size_t)k * f;
+    std::vector<uint8_t> ri((size_t)n * rw), vi((size_t)n * vw), out((size_t)n * f), st((size_t)n + 8, BFTKV_TH_FAILED);
+    std::vector<int32_t> xs((size_t)n * k);
+    for (uint32_t i = 0; i < n; ++i) {
+      memcpy(&ri[(size_t)i * rw], g[i]->th_a, rw);
+      memcpy(&vi[(size_t)i * vw], g[i]->th_b, vw);
+      memcpy(&xs[(size_t)i * k], g[i]->th_xs, (size_t)k * 4);
+    }
+    const int rc = ecdsa_calculate_r_impl(lane.ctx, n, k, xs.data(), ri.data(), vi.data(), r0.th_mod, r0.th_qbytes, out.data(), st.data(), false);
+    ++device_calls;
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(8) : st[i];
+      if (!rc && st[i] == 0) memcpy(r->th_out, &out[(size_t)i * f], f);
+    }
+  }
+
   void run_threshold(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const int kind = r0.kind;
+    if (kind == 8) { run_ecdsa(lane, g, device_calls); return; }
     const uint32_t n = (uint32_t)g.size(), k = r0.th_k, nb = r0.th_nbytes, qb = r0.th_qbytes;
     // (CalculateR: a group (p, q) is one table row)
     std::map<std::string, uint32_t> slot;
@@ -788,6 +812,22 @@ int bftkv_gpu_batcher_dsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const in
 int bftkv_gpu_batcher_modexp(bftkv_gpu_batcher* b, const uint8_t* base, uint32_t nbytes, const uint8_t* exp, uint32_t exp_len, const uint8_t* mod,
                              uint8_t* out, uint8_t* status_out) {
   return threshold_submit(b, 7, 1, nullptr, base, nbytes, exp, exp_len, mod, nullptr, out, nbytes, status_out);
+}
+
+int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                                        const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  const uint32_t f = (bit_size + 7) / 8;
+  if (r_out && bit_size && bit_size <= 521) memset(r_out, 0, f);
+  if (!b || !status_out || !r_out || !xs || !ri || !vi || !curve || bit_size == 0 || bit_size > 521 || k == 0 || k > 1024) return BFTKV_E_INVALID;
+  // refused for this caller alone, as an unsupported modulus is on the other threshold entries
+  if (ec_curve_id(curve, bit_size) < 0) return BFTKV_E_UNSUPPORTED;
+  bftkv_gpu_batcher::Req r{8, -4, nullptr, 0, nullptr, 0, false, 0};
+  r.th_shape = (uint64_t)8 | (uint64_t)k << 8 | (uint64_t)bit_size << 24;
+  r.th_k = k; r.th_nbytes = f; r.th_qbytes = bit_size; r.th_xs = xs; r.th_a = ri; r.th_b = vi; r.th_mod = curve; r.th_mod2 = nullptr; r.th_out = r_out;
+  const int rc = b->submit(r);
+  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
+  return rc;
 }
 
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]) {

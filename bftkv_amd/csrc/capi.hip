@@ -34,6 +34,7 @@
 #include "host_sha256.h"
 #include "kernels.hip"
 #include "threshold_kernels.hip"
+#include "ec_kernels.hip"
 
 using namespace bftkv;
 
@@ -156,6 +157,7 @@ struct bftkv_gpu_ctx {
   DevBuf st_tmp, item_tmp, bits_tmp, plan_cut;
   DevBuf chunk_arena, chunk_ctr;    // linearised partial-length signature bodies (parse_one) and their counters (k_walk / k_scan_counts)
   uint32_t multiexp_parts = 0;        // experiment knob (BFTKV_MULTIEXP_PARTS): quads per CalculateR operation, 0 = default policy
+  uint32_t ec_split = 0;              // experiment knob (BFTKV_EC_SPLIT): ECDSA CalculateR lanes, 1 = per term, 2 = per operation, 0 = default policy
   uint32_t multiexp_block = 0;        // experiment knob (BFTKV_MULTIEXP_BLOCK = 64): one-wave blocks for the 4-lane k_multiexp
   uint32_t multiexp_lanes = 0;        // experiment knob (BFTKV_MULTIEXP_LANES = 4 | 8): lanes per number in k_multiexp, 0 = by call size
   uint32_t dsa_inv_mode = 0;          // experiment knob (BFTKV_DSA_INV = single | batched): 1 / 2, 0 = by batch shape
@@ -1183,6 +1185,7 @@ int bftkv_gpu_init(int device_ordinal, bftkv_gpu_ctx** out) {
   if (const char* e = getenv("BFTKV_STAGED_SPIN_US")) c->staged_spin_us = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MODEXP_LDS_PAD")) c->modexp_lds_pad = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_PARTS")) c->multiexp_parts = (uint32_t)atoi(e);
+  if (const char* e = getenv("BFTKV_EC_SPLIT")) c->ec_split = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_LANES")) c->multiexp_lanes = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_BLOCK")) c->multiexp_block = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_DSA_INV")) c->dsa_inv_mode = !strcmp(e, "batched") ? 2u : !strcmp(e, "single") ? 1u : 0u;
@@ -2279,6 +2282,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 
 #include "rccl_capi.inc"
 #include "threshold_capi.inc"
+#include "ec_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

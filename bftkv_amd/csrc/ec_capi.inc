@@ -1,0 +1,186 @@
+// C ABI of the threshold-ECDSA entry points (include/bftkv_gpu.h): CalculateR and CalculatePartialR of
+// crypto/threshold/ecdsa/ecdsa.go over crypto/elliptic's four curves.  Kernels: ec_kernels.hip.
+namespace {
+
+// The groups the library recognises, by value: P, N, B, Gx, Gy (big-endian hex) and BitSize of crypto/elliptic's curves.  The
+// reference builds its group from the wire (ParseParams, ecdsa.go:105-123) and runs Go's generic a = -3 code on it; any other
+// group is refused for the whole call.
+struct EcNamedCurve {
+  uint32_t bits;
+  const char* hex[5];
+};
+const EcNamedCurve kEcCurves[4] = {
+    {224,
+     {"ffffffffffffffffffffffffffffffff000000000000000000000001", "ffffffffffffffffffffffffffff16a2e0b8f03e13dd29455c5c2a3d",
+      "b4050a850c04b3abf54132565044b0b7d7bfd8ba270b39432355ffb4", "b70e0cbd6bb4bf7f321390b94a03c1d356c21122343280d6115c1d21",
+      "bd376388b5f723fb4c22dfe6cd4375a05a07476444d5819985007e34"}},
+    {256,
+     {"ffffffff00000001000000000000000000000000ffffffffffffffffffffffff", "ffffffff00000000ffffffffffffffffbce6faada7179e84f3b9cac2fc632551",
+      "5ac635d8aa3a93e7b3ebbd55769886bc651d06b0cc53b0f63bce3c3e27d2604b", "6b17d1f2e12c4247f8bce6e563a440f277037d812deb33a0f4a13945d898c296",
+      "4fe342e2fe1a7f9b8ee7eb4a7c0f9e162bce33576b315ececbb6406837bf51f5"}},
+    {384,
+     {"fffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffeffffffff0000000000000000ffffffff",
+      "ffffffffffffffffffffffffffffffffffffffffffffffffc7634d81f4372ddf581a0db248b0a77aecec196accc52973",
+      "b3312fa7e23ee7e4988e056be3f82d19181d9c6efe8141120314088f5013875ac656398d8a2ed19d2a85c8edd3ec2aef",
+      "aa87ca22be8b05378eb1c71ef320ad746e1d3b628ba79b9859f741e082542a385502f25dbf55296c3a545e3872760ab7",
+      "3617de4a96262c6f5d9e98bf9292dc29f8f41dbd289a147ce9da3113b5f0b8c00a60b1ce1d7e819d7a431d7c90ea0e5f"}},
+    {521,
+     {"01ffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffff",
+      "01fffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffa51868783bf2f966b7fcc0148f709a5d03bb5c9b8899c47aebb6fb71e91386409",
+      "0051953eb9618e1c9a1f929a21a0b68540eea2da725b99b315f3b8b489918ef109e156193951ec7e937b1652c0bd3bb1bf073573df883d2c34f1ef451fd46b503f00",
+      "00c6858e06b70404e9cd9e3ecb662395b4429c648139053fb521f828af606b4d3dbaa14b5e77efe75928fe1dc127a2ffa8de3348b3c1856a429bf97e7e31c2e5bd66",
+      "011839296a789a3bc0045c8a5fb42c7d1bd998f54449579b446817afbd17273e662c97ee72995ef42640c550b9013fad0761353c7086a272c24088be94769fd16650"}},
+};
+
+// curve: P || N || B || Gx || Gy, (bit_size + 7) / 8 bytes each.  Index into kEcCurves, or -1.
+int ec_curve_id(const uint8_t* curve, uint32_t bit_size) {
+  for (int id = 0; id < 4; ++id) {
+    const EcNamedCurve& nc = kEcCurves[id];
+    if (nc.bits != bit_size) continue;
+    const uint32_t f = (bit_size + 7) / 8;
+    bool same = true;
+    for (int part = 0; part < 5 && same; ++part)
+      for (uint32_t i = 0; i < f && same; ++i) {
+        const char* h = nc.hex[part] + 2 * i;
+        auto nib = [](char ch) { return (uint32_t)(ch <= '9' ? ch - '0' : ch - 'a' + 10); };
+        same = curve[(size_t)part * f + i] == (uint8_t)(nib(h[0]) << 4 | nib(h[1]));
+      }
+    if (same) return id;
+  }
+  return -1;
+}
+
+// The word count per curve: 7, 8, 12, 17.  f(ecf::Curve<L>) is called with the curve's constants, built on the host.
+template <typename F>
+void ec_dispatch(int id, const uint8_t* curve, F&& f) {
+  const uint32_t fb = (kEcCurves[id].bits + 7) / 8;
+  switch (id) {
+    case 0: { ecf::Curve<7> C; ecf::curve_setup<7>(C, curve, fb); f(C); break; }
+    case 1: { ecf::Curve<8> C; ecf::curve_setup<8>(C, curve, fb); f(C); break; }
+    case 2: { ecf::Curve<12> C; ecf::curve_setup<12>(C, curve, fb); f(C); break; }
+    default: { ecf::Curve<17> C; ecf::curve_setup<17>(C, curve, fb); f(C); break; }
+  }
+}
+
+// status bytes start out as BFTKV_TH_FAILED: whatever the call does not reach stays a failure
+int ec_status_failed(bftkv_gpu_ctx* c, uint8_t* status_out, uint32_t n_ops, bool dev) {
+  if (dev) HIPCHK(c, hipMemsetAsync(status_out, BFTKV_TH_FAILED, n_ops, c->stream));
+  else memset(status_out, BFTKV_TH_FAILED, n_ops);
+  return 0;
+}
+
+int ecdsa_calculate_r_impl(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                           const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out, bool dev) {
+  if (!c || !curve || bit_size == 0 || bit_size > 521 || k == 0 || k > 1024 || (uint64_t)n_ops * k > (1u << 24) ||
+      (n_ops && (!xs || !ri || !vi || !r_out || !status_out)))
+    return BFTKV_E_INVALID;
+  const int id = ec_curve_id(curve, bit_size);
+  if (id < 0) return BFTKV_E_UNSUPPORTED;
+  if (n_ops == 0) return 0;
+  const uint32_t f = (bit_size + 7) / 8;
+  ctx_lock lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
+  ScratchBufs sb(c);
+  { int grc = modtab_gc(c); if (grc) return grc; }
+  ModTab mq;
+  uint32_t *d_vi, *d_gi;
+  int32_t* d_xs;
+  uint8_t* d_ri;
+  void *d_inv, *d_st, *d_lam, *d_v, *d_vinv, *d_r;
+  const size_t nk = (size_t)n_ops * k, rw = 1 + 2 * (size_t)f;
+  if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq))) return rc;                  // N: the Lagrange coefficients and v live mod N
+  if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;           // (one group per call: every index 0)
+  if ((rc = to_dev_limbs(c, sb, vi, nk, f, &d_vi, dev))) return rc;
+  if ((rc = to_dev(c, sb, xs, nk, &d_xs, dev))) return rc;
+  if ((rc = to_dev(c, sb, ri, nk * rw, &d_ri, dev))) return rc;
+  if ((rc = dev_alloc(c, sb, nk * MONT_N * 4, &d_inv, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_st, true)) ||
+      (rc = dev_alloc(c, sb, nk * MONT_N * 4, &d_lam, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_v, false)) ||
+      (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_vinv, false)))
+    return rc;
+  if (dev) d_r = r_out;
+  else if ((rc = dev_alloc(c, sb, (size_t)n_ops * f, &d_r, false))) return rc;
+  hipStream_t s = c->stream;
+  // l_j mod N (written out: they become scalars) and v = sum Vi_j l_j mod N, exactly as on the DSA path
+  hipLaunchKernelGGL(k_lagrange_inv, dim3((uint32_t)((nk + 63) / 64)), dim3(64), 0, s, n_ops, k, d_xs, d_gi, mq, (uint32_t*)d_inv, (uint8_t*)d_st);
+  hipLaunchKernelGGL(k_lagrange_terms, quad_grid(n_ops), dim3(RSA_BLOCK), 0, s, n_ops, k, (uint32_t*)d_inv, d_vi, d_gi, mq, (uint32_t*)d_lam,
+                     (uint32_t*)d_v, (const uint8_t*)d_st);
+  if (dev ? !lagrange_bound_says_small(c, k) : lagrange_needs_big(xs, n_ops, k))
+    if ((rc = lagrange_big_path(c, sb, n_ops, k, d_xs, d_vi, d_gi, mq, (uint32_t*)d_lam, (uint32_t*)d_v, (uint8_t*)d_st, f))) return rc;
+  // w = v^-1 mod N (N is up to 521 bits: the general inverse, not the 256-bit one); v = 0 sets status bit 1
+  hipLaunchKernelGGL(k_modinv, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint32_t*)d_v, (const uint32_t*)d_gi, mq, (uint32_t*)d_vinv,
+                     (uint8_t*)d_st, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+  // The work split (DESIGN.md section 3): a lane per (operation, term) and an ordered fold per operation.  One lane per operation
+  // (BFTKV_EC_SPLIT=2) measured 2.9-4.0x slower at 10,000 operations and 5-13x for a lone call (k = 8 and 22, P-224 to P-384): it
+  // leaves k times fewer waves to hide 256-VGPR latencies with.
+  const bool per_op = c->ec_split == 2;
+  void* d_t = nullptr;
+  ec_dispatch(id, curve, [&](auto C) {
+    constexpr int L = decltype(C)::kWords;
+    if constexpr (L <= 12) {       // (P-521: a term and a running sum in one lane do not fit 256 VGPRs without scratch)
+      if (per_op) {
+        hipLaunchKernelGGL(k_ec_calc_r_op<L>, dim3((n_ops + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, s, n_ops, k, (const uint8_t*)d_ri,
+                           (const uint32_t*)d_lam, (const uint32_t*)d_vinv, C, (uint8_t*)d_st, (uint8_t*)d_r);
+        return;
+      }
+    }
+    if ((rc = dev_alloc(c, sb, nk * 3 * L * 4, &d_t, false))) return;
+    hipLaunchKernelGGL(k_ec_terms<L>, dim3((uint32_t)((nk + EC_BLOCK - 1) / EC_BLOCK)), dim3(EC_BLOCK), 0, s, n_ops, k, (const uint8_t*)d_ri,
+                       (const uint32_t*)d_lam, (const uint32_t*)d_vinv, C, (uint32_t*)d_t, (uint8_t*)d_st);
+    hipLaunchKernelGGL(k_ec_fold<L>, dim3((n_ops + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, s, n_ops, k, (const uint32_t*)d_t, C, (uint8_t*)d_st,
+                       (uint8_t*)d_r);
+  });
+  if (rc) return rc;
+  if (!dev) HIPCHK(c, hipMemcpyAsync(r_out, d_r, (size_t)n_ops * f, hipMemcpyDeviceToHost, s));
+  if ((rc = copy_status(c, status_out, d_st, n_ops, dev))) return rc;
+  return finish(c, dev);
+}
+
+int ec_scalar_base_mult_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* scalars, uint32_t sbytes, const uint8_t* curve, uint32_t bit_size,
+                             uint8_t* out, uint8_t* status_out) {
+  if (!c || !curve || bit_size == 0 || bit_size > 521 || n_ops > (1u << 24) || (n_ops && (!scalars || !out || !status_out))) return BFTKV_E_INVALID;
+  const int id = ec_curve_id(curve, bit_size);
+  if (id < 0) return BFTKV_E_UNSUPPORTED;
+  const uint32_t f = (bit_size + 7) / 8;
+  if (sbytes == 0 || sbytes > f) return BFTKV_E_INVALID;
+  if (n_ops == 0) return 0;
+  ctx_lock lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ec_status_failed(c, status_out, n_ops, false))) return rc;
+  ScratchBufs sb(c);
+  uint8_t* d_s;
+  void *d_out, *d_st;
+  const size_t ow = 1 + 2 * (size_t)f;
+  if ((rc = to_dev(c, sb, scalars, (size_t)n_ops * sbytes, &d_s))) return rc;
+  if ((rc = dev_alloc(c, sb, (size_t)n_ops * ow, &d_out, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_st, false))) return rc;
+  hipStream_t s = c->stream;
+  ec_dispatch(id, curve, [&](auto C) {
+    constexpr int L = decltype(C)::kWords;
+    hipLaunchKernelGGL(k_ec_base_mult<L>, dim3((n_ops + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, s, n_ops, (const uint8_t*)d_s, sbytes, C,
+                       (uint8_t*)d_out, (uint8_t*)d_st);
+  });
+  HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_ops * ow, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
+  return finish(c, false);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bftkv_gpu_ecdsa_calculate_r(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                                const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out) {
+  return ecdsa_calculate_r_impl(c, n_ops, k, xs, ri, vi, curve, bit_size, r_out, status_out, false);
+}
+int bftkv_gpu_ecdsa_calculate_r_dev(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                                    const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out) {
+  return ecdsa_calculate_r_impl(c, n_ops, k, xs, ri, vi, curve, bit_size, r_out, status_out, true);
+}
+int bftkv_gpu_ec_scalar_base_mult(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* scalars, uint32_t sbytes, const uint8_t* curve,
+                                  uint32_t bit_size, uint8_t* out, uint8_t* status_out) {
+  return ec_scalar_base_mult_impl(c, n_ops, scalars, sbytes, curve, bit_size, out, status_out);
+}
+
+}  // extern "C"

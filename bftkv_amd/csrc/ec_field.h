@@ -1,0 +1,340 @@
+// Field and point arithmetic of the NIST prime curves (crypto/elliptic's P-224, P-256, P-384, P-521: a = -3, prime order,
+// cofactor 1) for the threshold-ECDSA kernels of ec_kernels.hip.  The same text compiles for the host (tests/c/ec_host.cpp
+// checks it against the Python restatement in the CPU suite), so everything here is plain C++ behind EC_HD.
+//
+// Field elements are L little-endian 32-bit words (L = 7, 8, 12, 17), kept fully reduced in [0, p) in Montgomery form
+// (R = 2^(32 L)): one product is CIOS Montgomery, 2 L^2 32x32->64 multiply-adds (one v_mad_u64_u32 each), and a reduced
+// representation makes "is zero" and "equal" plain word compares -- what the exceptional cases of point addition need.
+// Points are Jacobian (X : Y : Z), Z = 0 is the point at infinity.
+#pragma once
+#include <stdint.h>
+
+#ifndef EC_HD
+#if defined(__HIPCC__) || defined(__HIP__)
+#define EC_HD __host__ __device__ __forceinline__
+#else
+#define EC_HD static inline
+#endif
+#endif
+
+namespace ecf {
+
+template <int L>
+struct Curve {
+  static constexpr int kWords = L;
+  uint32_t p[L], n[L];        // field prime, group order
+  uint32_t rr_p[L], rr_n[L];  // R^2 mod p, R^2 mod n
+  uint32_t one[L];            // R mod p (1 in Montgomery form)
+  uint32_t b[L];              // B R mod p
+  uint32_t gx[L], gy[L];      // the base point, Montgomery form
+  uint32_t pm2[L];            // p - 2 (Fermat's exponent)
+  uint32_t p0inv, n0inv;      // -p^-1, -n^-1 mod 2^32
+  uint32_t fbytes;            // (BitSize + 7) / 8
+};
+
+template <int L>
+struct Jac {
+  uint32_t x[L], y[L], z[L];
+};
+
+// ---- words -----------------------------------------------------------------------------------------------------------
+template <int L>
+EC_HD void fe_copy(uint32_t* r, const uint32_t* a) {
+#pragma unroll
+  for (int i = 0; i < L; ++i) r[i] = a[i];
+}
+template <int L>
+EC_HD void fe_zero(uint32_t* r) {
+#pragma unroll
+  for (int i = 0; i < L; ++i) r[i] = 0;
+}
+template <int L>
+EC_HD bool fe_is_zero(const uint32_t* a) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) o |= a[i];
+  return o == 0;
+}
+template <int L>
+EC_HD bool fe_eq(const uint32_t* a, const uint32_t* b) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) o |= a[i] ^ b[i];
+  return o == 0;
+}
+template <int L>
+EC_HD bool fe_lt(const uint32_t* a, const uint32_t* m) {        // a < m
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) br = ((uint64_t)a[i] - m[i] - br) >> 63;
+  return br != 0;
+}
+// big-endian bytes (len <= 4 L) -> words
+template <int L>
+EC_HD void fe_from_be(uint32_t* r, const uint8_t* s, uint32_t len) {
+  fe_zero<L>(r);
+  for (uint32_t i = 0; i < len; ++i) {
+    const uint32_t bit = 8u * (len - 1u - i);
+    r[bit >> 5] |= (uint32_t)s[i] << (bit & 31u);
+  }
+}
+template <int L>
+EC_HD void fe_to_be(uint8_t* d, uint32_t len, const uint32_t* a) {
+  for (uint32_t i = 0; i < len; ++i) {
+    const uint32_t bit = 8u * (len - 1u - i);
+    d[i] = (uint8_t)(a[bit >> 5] >> (bit & 31u));
+  }
+}
+
+// ---- arithmetic mod m (inputs in [0, m)) --------------------------------------------------------------------------
+template <int L>
+EC_HD void fe_add(uint32_t* r, const uint32_t* a, const uint32_t* b, const uint32_t* m) {
+  uint32_t s[L], d[L];
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) { c += (uint64_t)a[i] + b[i]; s[i] = (uint32_t)c; c >>= 32; }
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) { const uint64_t v = (uint64_t)s[i] - m[i] - br; d[i] = (uint32_t)v; br = v >> 63; }
+  const bool use_d = c || !br;     // a + b >= m
+#pragma unroll
+  for (int i = 0; i < L; ++i) r[i] = use_d ? d[i] : s[i];
+}
+template <int L>
+EC_HD void fe_sub(uint32_t* r, const uint32_t* a, const uint32_t* b, const uint32_t* m) {
+  uint32_t d[L];
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) { const uint64_t v = (uint64_t)a[i] - b[i] - br; d[i] = (uint32_t)v; br = v >> 63; }
+  const uint32_t mask = br ? 0xFFFFFFFFu : 0u;
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) { c += (uint64_t)d[i] + (m[i] & mask); r[i] = (uint32_t)c; c >>= 32; }
+}
+// CIOS Montgomery product a b R^-1 mod m (a, b < m < 2^(32 L)); r may alias a or b.  The outer loop stays rolled (the
+// product is inlined some forty times per kernel) and walks b by rotating a copy, so every index is a constant and nothing
+// leaves registers.
+template <int L>
+EC_HD void fe_mul(uint32_t* r, const uint32_t* a, const uint32_t* b, const uint32_t* m, uint32_t m0inv) {
+  uint32_t t[L + 2], bw[L];
+#pragma unroll
+  for (int j = 0; j < L + 2; ++j) t[j] = 0;
+#pragma unroll
+  for (int j = 0; j < L; ++j) bw[j] = b[j];
+#pragma unroll 1
+  for (int i = 0; i < L; ++i) {
+    const uint32_t bi = bw[0];
+#pragma unroll
+    for (int j = 0; j + 1 < L; ++j) bw[j] = bw[j + 1];
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < L; ++j) { c = (uint64_t)a[j] * bi + t[j] + (c >> 32); t[j] = (uint32_t)c; }
+    c = (uint64_t)t[L] + (c >> 32);
+    t[L] = (uint32_t)c;
+    t[L + 1] = (uint32_t)(c >> 32);
+    const uint32_t q = t[0] * m0inv;
+    c = (uint64_t)q * m[0] + t[0];
+#pragma unroll
+    for (int j = 1; j < L; ++j) { c = (uint64_t)q * m[j] + t[j] + (c >> 32); t[j - 1] = (uint32_t)c; }
+    c = (uint64_t)t[L] + (c >> 32);
+    t[L - 1] = (uint32_t)c;
+    t[L] = t[L + 1] + (uint32_t)(c >> 32);
+  }
+  uint32_t d[L];       // t < 2m: one conditional subtraction
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) { const uint64_t v = (uint64_t)t[i] - m[i] - br; d[i] = (uint32_t)v; br = v >> 63; }
+  const bool use_d = t[L] || !br;
+#pragma unroll
+  for (int i = 0; i < L; ++i) r[i] = use_d ? d[i] : t[i];
+}
+
+template <int L> EC_HD void fp_mul(uint32_t* r, const uint32_t* a, const uint32_t* b, const Curve<L>& C) { fe_mul<L>(r, a, b, C.p, C.p0inv); }
+template <int L> EC_HD void fp_sqr(uint32_t* r, const uint32_t* a, const Curve<L>& C) { fe_mul<L>(r, a, a, C.p, C.p0inv); }
+template <int L> EC_HD void fp_add(uint32_t* r, const uint32_t* a, const uint32_t* b, const Curve<L>& C) { fe_add<L>(r, a, b, C.p); }
+template <int L> EC_HD void fp_sub(uint32_t* r, const uint32_t* a, const uint32_t* b, const Curve<L>& C) { fe_sub<L>(r, a, b, C.p); }
+
+// a^(p-2) = a^-1 (Montgomery form in and out; 0 -> 0): left-to-right square and multiply over the bits of p - 2
+template <int L>
+EC_HD void fp_inv(uint32_t* r, const uint32_t* a, const Curve<L>& C) {
+  uint32_t acc[L];
+  fe_copy<L>(acc, C.one);
+  for (int i = 32 * L - 1; i >= 0; --i) {
+    fp_sqr<L>(acc, acc, C);
+    if ((C.pm2[i >> 5] >> (i & 31)) & 1u) fp_mul<L>(acc, acc, a, C);
+  }
+  fe_copy<L>(r, acc);
+}
+
+// ---- points --------------------------------------------------------------------------------------------------------
+template <int L>
+EC_HD bool pt_is_inf(const Jac<L>& P) { return fe_is_zero<L>(P.z); }
+template <int L>
+EC_HD void pt_set_inf(Jac<L>& P) { fe_zero<L>(P.x); fe_zero<L>(P.y); fe_zero<L>(P.z); }
+
+// 2P with a = -3 (dbl-2001-b, the formula of Go's doubleJacobian); infinity stays infinity (Z3 = (Y+0)^2 - Y^2 = 0).  The
+// curves have prime order, so no finite point has Y = 0.  R may alias P.
+template <int L>
+EC_HD void pt_dbl(Jac<L>& R, const Jac<L>& P, const Curve<L>& C) {
+  uint32_t delta[L], gamma[L], beta[L], alpha[L], t[L], u[L];
+  fp_sqr<L>(delta, P.z, C);
+  fp_sqr<L>(gamma, P.y, C);
+  fp_mul<L>(beta, P.x, gamma, C);
+  fp_sub<L>(t, P.x, delta, C);
+  fp_add<L>(u, P.x, delta, C);
+  fp_mul<L>(alpha, t, u, C);
+  fp_add<L>(t, alpha, alpha, C);
+  fp_add<L>(alpha, alpha, t, C);                        // alpha = 3 (X - delta)(X + delta)
+  fp_add<L>(u, P.y, P.z, C);
+  fp_sqr<L>(u, u, C);
+  fp_sub<L>(u, u, gamma, C);
+  fp_sub<L>(R.z, u, delta, C);                          // Z3 = (Y + Z)^2 - gamma - delta   (P.z is dead from here)
+  fp_add<L>(beta, beta, beta, C);
+  fp_add<L>(beta, beta, beta, C);                       // 4 beta
+  fp_sqr<L>(t, alpha, C);
+  fp_add<L>(u, beta, beta, C);
+  fp_sub<L>(R.x, t, u, C);                              // X3 = alpha^2 - 8 beta
+  fp_sub<L>(t, beta, R.x, C);
+  fp_mul<L>(t, alpha, t, C);
+  fp_sqr<L>(gamma, gamma, C);
+  fp_add<L>(gamma, gamma, gamma, C);
+  fp_add<L>(gamma, gamma, gamma, C);
+  fp_add<L>(gamma, gamma, gamma, C);                    // 8 gamma^2
+  fp_sub<L>(R.y, t, gamma, C);                          // Y3 = alpha (4 beta - X3) - 8 gamma^2
+}
+
+// What pt_add met (the fold's fence rules need to know; the result is exact in every case)
+enum { EC_ADD_GENERAL = 0, EC_ADD_EQUAL = 1, EC_ADD_OPPOSITE = 2, EC_ADD_INF_OPERAND = 3 };
+
+// P + Q, exact for every input: an operand at infinity, P == Q (doubling), P == -Q (infinity).  R may alias P or Q.
+template <int L>
+EC_HD int pt_add(Jac<L>& R, const Jac<L>& P, const Jac<L>& Q, const Curve<L>& C) {
+  if (pt_is_inf<L>(P)) { R = Q; return EC_ADD_INF_OPERAND; }
+  if (pt_is_inf<L>(Q)) { R = P; return EC_ADD_INF_OPERAND; }
+  uint32_t u1[L], s1[L], h[L], rr[L], t[L], v[L];
+  fp_sqr<L>(t, Q.z, C);
+  fp_mul<L>(u1, P.x, t, C);                             // U1 = X1 Z2^2
+  fp_mul<L>(t, t, Q.z, C);
+  fp_mul<L>(s1, P.y, t, C);                             // S1 = Y1 Z2^3
+  fp_sqr<L>(t, P.z, C);
+  fp_mul<L>(h, Q.x, t, C);                              // U2
+  fp_sub<L>(h, h, u1, C);                               // H = U2 - U1
+  fp_mul<L>(t, t, P.z, C);
+  fp_mul<L>(rr, Q.y, t, C);                             // S2
+  fp_sub<L>(rr, rr, s1, C);                             // r = S2 - S1
+  if (fe_is_zero<L>(h)) {
+    if (fe_is_zero<L>(rr)) { pt_dbl<L>(R, P, C); return EC_ADD_EQUAL; }
+    pt_set_inf<L>(R);
+    return EC_ADD_OPPOSITE;
+  }
+  fp_mul<L>(t, P.z, Q.z, C);
+  fp_mul<L>(R.z, t, h, C);                              // Z3 = Z1 Z2 H
+  fp_sqr<L>(t, h, C);                                   // H^2
+  fp_mul<L>(v, u1, t, C);                               // V = U1 H^2
+  fp_mul<L>(h, h, t, C);                                // H^3
+  fp_mul<L>(s1, s1, h, C);                              // S1 H^3
+  fp_sqr<L>(t, rr, C);
+  fp_sub<L>(t, t, h, C);
+  fp_sub<L>(t, t, v, C);
+  fp_sub<L>(R.x, t, v, C);                              // X3 = r^2 - H^3 - 2 V
+  fp_sub<L>(t, v, R.x, C);
+  fp_mul<L>(t, rr, t, C);
+  fp_sub<L>(R.y, t, s1, C);                             // Y3 = r (V - X3) - S1 H^3
+  return EC_ADD_GENERAL;
+}
+
+// k P, left to right over the bits of k (L words), one doubling per bit and one addition per set bit.  Exact whatever k
+// (k >= n included): every addition goes through pt_add.
+template <int L>
+EC_HD void pt_mul(Jac<L>& R, const Jac<L>& P, const uint32_t* k, const Curve<L>& C) {
+  Jac<L> acc;
+  pt_set_inf<L>(acc);
+  int top = 32 * L - 1;
+  while (top >= 0 && !((k[top >> 5] >> (top & 31)) & 1u)) --top;
+  for (int i = top; i >= 0; --i) {
+    pt_dbl<L>(acc, acc, C);
+    if ((k[i >> 5] >> (i & 31)) & 1u) pt_add<L>(acc, acc, P, C);
+  }
+  R = acc;
+}
+
+// affine coordinates, plain (out of Montgomery form); infinity -> (0, 0) as Go's affineFromJacobian
+template <int L>
+EC_HD void pt_affine(uint32_t* x, uint32_t* y, const Jac<L>& P, const Curve<L>& C) {
+  if (pt_is_inf<L>(P)) { fe_zero<L>(x); fe_zero<L>(y); return; }
+  uint32_t zi[L], z2[L], t[L], one_plain[L];
+  fp_inv<L>(zi, P.z, C);
+  fp_sqr<L>(z2, zi, C);
+  fe_zero<L>(one_plain);
+  one_plain[0] = 1;
+  fp_mul<L>(t, P.x, z2, C);
+  fp_mul<L>(x, t, one_plain, C);
+  fp_mul<L>(z2, z2, zi, C);
+  fp_mul<L>(t, P.y, z2, C);
+  fp_mul<L>(y, t, one_plain, C);
+}
+
+// Go's Unmarshal checks on plain coordinates x, y: both below p and y^2 = x^3 - 3 x + B.  On success xm / ym are the
+// Montgomery forms.
+template <int L>
+EC_HD bool pt_check(uint32_t* xm, uint32_t* ym, const uint32_t* x, const uint32_t* y, const Curve<L>& C) {
+  if (!fe_lt<L>(x, C.p) || !fe_lt<L>(y, C.p)) return false;
+  uint32_t l[L], r[L], t[L];
+  fp_mul<L>(xm, x, C.rr_p, C);
+  fp_mul<L>(ym, y, C.rr_p, C);
+  fp_sqr<L>(l, ym, C);
+  fp_sqr<L>(r, xm, C);
+  fp_mul<L>(r, r, xm, C);
+  fp_add<L>(t, xm, xm, C);
+  fp_add<L>(t, t, xm, C);
+  fp_sub<L>(r, r, t, C);
+  fp_add<L>(r, r, C.b, C);
+  return fe_eq<L>(l, r);
+}
+
+// a b mod n for a, b < n (plain in, plain out): two Montgomery products under n
+template <int L>
+EC_HD void fn_mul(uint32_t* r, const uint32_t* a, const uint32_t* b, const Curve<L>& C) {
+  uint32_t t[L];
+  fe_mul<L>(t, a, b, C.n, C.n0inv);
+  fe_mul<L>(r, t, C.rr_n, C.n, C.n0inv);
+}
+
+// ---- constants, on the host (once per curve and context) -------------------------------------------------------------
+EC_HD uint32_t neg_inv32(uint32_t m0) {      // -m0^-1 mod 2^32 (m0 odd), Newton
+  uint32_t x = m0;
+  for (int i = 0; i < 5; ++i) x *= 2u - m0 * x;
+  return 0u - x;
+}
+template <int L>
+EC_HD void r_powers(uint32_t* r1, uint32_t* r2, const uint32_t* m) {    // R mod m, R^2 mod m by doubling (odd m < R)
+  uint32_t t[L];
+  fe_zero<L>(t);
+  t[0] = 1;
+  for (int i = 0; i < 32 * L; ++i) fe_add<L>(t, t, t, m);
+  fe_copy<L>(r1, t);
+  for (int i = 0; i < 32 * L; ++i) fe_add<L>(t, t, t, m);
+  fe_copy<L>(r2, t);
+}
+// P, N, B, Gx, Gy: big-endian, fbytes each
+template <int L>
+EC_HD void curve_setup(Curve<L>& C, const uint8_t* be, uint32_t fbytes) {
+  uint32_t bb[L], g[L], r1n[L];
+  C.fbytes = fbytes;
+  fe_from_be<L>(C.p, be, fbytes);
+  fe_from_be<L>(C.n, be + fbytes, fbytes);
+  C.p0inv = neg_inv32(C.p[0]);
+  C.n0inv = neg_inv32(C.n[0]);
+  r_powers<L>(C.one, C.rr_p, C.p);
+  r_powers<L>(r1n, C.rr_n, C.n);
+  fe_from_be<L>(bb, be + 2 * fbytes, fbytes);
+  fp_mul<L>(C.b, bb, C.rr_p, C);
+  fe_from_be<L>(g, be + 3 * fbytes, fbytes);
+  fp_mul<L>(C.gx, g, C.rr_p, C);
+  fe_from_be<L>(g, be + 4 * fbytes, fbytes);
+  fp_mul<L>(C.gy, g, C.rr_p, C);
+  uint64_t br = 2;
+  for (int i = 0; i < L; ++i) { const uint64_t v = (uint64_t)C.p[i] - br; C.pm2[i] = (uint32_t)v; br = v >> 63; }
+}
+
+}  // namespace ecf

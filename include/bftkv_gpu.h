@@ -379,6 +379,12 @@ int bftkv_gpu_batcher_dsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const in
  * decides whether they may leave the host (the shim leaves these two on the CPU unless asked). */
 int bftkv_gpu_batcher_modexp(bftkv_gpu_batcher* b, const uint8_t* base, uint32_t nbytes, const uint8_t* exp, uint32_t exp_len,
                              const uint8_t* mod, uint8_t* out, uint8_t* status_out);
+/* ecdsaGroupOperations.CalculateR (crypto/threshold/ecdsa/ecdsa.go:36-59) for ONE operation: xs [k], ri [k][1 + 2 fbytes],
+ * vi [k][fbytes], r_out [fbytes]; curve and bit_size as for bftkv_gpu_ecdsa_calculate_r.  Callers on different curves may
+ * share a batcher (each curve gets its own device call); an unrecognised group returns BFTKV_E_UNSUPPORTED for that caller
+ * alone, and a caller's fenced operation fences no one else's. */
+int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                                        const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -506,6 +512,35 @@ int bftkv_gpu_sss_distribute_dev(bftkv_gpu_ctx* ctx, uint32_t n_polys, uint32_t 
                                  const uint32_t* mod_idx, uint32_t n_mods, const uint8_t* mods, uint8_t* shares_out);
 int bftkv_gpu_modinv_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* values, uint32_t nbytes, const uint32_t* mod_idx, uint32_t n_mods,
                          const uint8_t* mods, uint8_t* out, uint8_t* status_out);
+
+/* ---- threshold ECDSA (crypto/threshold/ecdsa/ecdsa.go) ------------------------------------------ */
+/* The group of a combine comes from the wire (ParseParams, ecdsa.go:105-123): a bare elliptic.CurveParams on which Go runs its
+ * generic a = -3 Jacobian code.  `curve` is P || N || B || Gx || Gy, fbytes big-endian bytes each, fbytes = (bit_size + 7) / 8;
+ * the library recognises by value exactly crypto/elliptic's P-224, P-256, P-384 and P-521 (all six values equal) and returns
+ * BFTKV_E_UNSUPPORTED for the whole call on any other group.
+ *
+ * ecdsaGroupOperations.CalculateR (ecdsa.go:36-59), n_ops operations of k shares (1 <= k <= 1024, n_ops * k <= 2^24):
+ *   xs [n_ops][k] int32; ri [n_ops][k][1 + 2 fbytes] the partial Rs as elliptic.Marshal wrote them; vi [n_ops][k][fbytes];
+ *   r_out [n_ops][fbytes]: r = x(w sum_j l_j R_j) mod N, w = (sum_j Vi_j l_j)^-1 mod N, l_j = sss.Lagrange(x_j, xs, N).
+ * A Vi wider than fbytes, or a partial R of another length, is not submitted: the caller keeps the reference path.
+ *   status_out    BFTKV_TH_OK (r_out holds r; 0 when the final sum is the point at infinity);
+ *                 BFTKV_TH_NO_INVERSE (v = 0 mod N: ModInverse fails);
+ *                 BFTKV_TH_FENCED (the reference decides, r_out zero): a partial R that elliptic.Unmarshal refuses (length is
+ *                 the caller's, then prefix 0x04, coordinates below P, on the curve), some l_j = 0 mod N, a prefix sum at
+ *                 infinity before the last term or equal to the next term (Add's doubling case), Lagrange integers beyond
+ *                 2128 bits (docs/parity.md, "Rules that rest on memory");
+ *                 BFTKV_TH_FAILED whenever the return code is not 0 (the bytes start out as failures). */
+int bftkv_gpu_ecdsa_calculate_r(bftkv_gpu_ctx* ctx, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                                const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out);
+/* same with xs / ri / vi / r_out / status_out resident in HBM, asynchronous on the context's stream (curve stays a host
+ * pointer); bftkv_gpu_set_lagrange_x_bound applies as for the other _dev forms. */
+int bftkv_gpu_ecdsa_calculate_r_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
+                                    const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out);
+/* ecdsaGroupOperations.CalculatePartialR (ecdsa.go:31-34): out[i] = elliptic.Marshal(ScalarBaseMult(scalars[i])),
+ * [n_ops][1 + 2 fbytes]; scalars [n_ops][sbytes] big-endian, 1 <= sbytes <= fbytes.  0 gives 04 || 0...0.  A scalar >= N never
+ * comes from the reference (a share mod N): BFTKV_TH_FENCED and zeroes.  status_out [n_ops] as above. */
+int bftkv_gpu_ec_scalar_base_mult(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* scalars, uint32_t sbytes, const uint8_t* curve,
+                                  uint32_t bit_size, uint8_t* out, uint8_t* status_out);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

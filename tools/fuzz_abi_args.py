@@ -165,6 +165,50 @@ def threshold_one():
     note(name, rc)
 
 
+_EC = __import__("json").load(open(os.path.join(ROOT, "tests", "golden", "ec_curves.json")))
+
+
+def ec_curve(bits):
+    """P || N || B || Gx || Gy of a recognised curve when `bits` names one (sometimes with one byte changed), else random bytes."""
+    f = (bits + 7) // 8
+    named = [c for c in _EC.values() if c["bit_size"] == bits]
+    if not named or rng.random() < 0.2:
+        return buf(5 * f)
+    cb = bytearray(b"".join(int(named[0][key], 16).to_bytes(f, "big") for key in ("p", "n", "b", "gx", "gy")))
+    if rng.random() < 0.2:
+        cb[rng.randrange(len(cb))] ^= 1 << rng.randrange(8)
+    return np.frombuffer(bytes(cb), dtype=np.uint8).copy()
+
+
+def ecdsa_calls():
+    bits = rng.choice([0, 1, 8, 224, 255, 256, 384, 521, 522, 4096])
+    f = (bits + 7) // 8
+    n_ops = rng.choice([0, 0, 1, 2, 5, 64])
+    k = small(KS, 1 << 22, max(n_ops, 1) * (1 + 2 * f))
+    cb = ec_curve(bits) if rng.random() < 0.95 else None
+    st = buf(n_ops, "zero")
+    which = rng.randrange(4)
+    if which < 2:
+        null = n_ops == 0 and rng.random() < 0.5
+        xs, ri, vi, r_out = xs_of(n_ops * k), buf(n_ops * k * (1 + 2 * f)), buf(n_ops * k * f), buf(n_ops * max(f, 1), "zero")
+        fn = lib.bftkv_gpu_ecdsa_calculate_r if which == 0 else lib.bftkv_gpu_ecdsa_calculate_r_dev
+        args = (None, None, None) if null else (xs.ctypes.data_as(vp), p8(ri), p8(vi))
+        note("ecdsa_calculate_r" + ("_dev" if which else ""), fn(ctx, n_ops, k, *args, p8(cb) if cb is not None else None, bits,
+                                                                 None if null else p8(r_out), None if null else p8(st)))
+    elif which == 2:
+        sb = rng.choice([0, 1, 2, f - 1, f, f + 1, 1024])
+        sb = max(sb, 0)
+        sc, out = buf(n_ops * sb), buf(n_ops * (1 + 2 * f), "zero")
+        note("ec_scalar_base_mult", lib.bftkv_gpu_ec_scalar_base_mult(ctx, n_ops, p8(sc), sb, p8(cb) if cb is not None else None, bits, p8(out), p8(st)))
+    else:
+        k = small(KS, 1 << 20, 1 + 2 * f)
+        out, s1 = buf(max(f, 1), "zero"), C.c_uint8(0x55)
+        rc = lib.bftkv_gpu_batcher_ecdsa_calculate_r(batcher, k, xs_of(k).ctypes.data_as(vp), p8(buf(k * (1 + 2 * f))), p8(buf(k * f)),
+                                                     p8(cb) if cb is not None else None, bits, p8(out), C.byref(s1))
+        assert rc == 0 or s1.value == 0xFF, ("batcher_ecdsa_calculate_r", rc, s1.value)      # fail closed
+        note("batcher_ecdsa_calculate_r", rc)
+
+
 def offsets(n, total):
     o = np.zeros(n + 1, dtype=np.uint64)
     style = rng.random()
@@ -319,7 +363,8 @@ assert lib.bftkv_gpu_quorum_create(ctx, qc0, 1, C.byref(quorum)) == 0
 t0 = time.time()
 n = 0
 while time.time() - t0 < budget:
-    rng.choice([threshold_batched, threshold_batched, threshold_one, verify_calls, verify_calls, keyring_and_quorum, cert_calls, cert_calls])()
+    rng.choice([threshold_batched, threshold_batched, threshold_one, verify_calls, verify_calls, keyring_and_quorum, cert_calls, cert_calls,
+                ecdsa_calls])()
     n += 1
 lib.bftkv_gpu_batcher_destroy(batcher)
 lib.bftkv_gpu_destroy(ctx)

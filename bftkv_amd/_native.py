@@ -48,6 +48,7 @@ EXPORTS = [
     "bftkv_gpu_set_host_pipeline", "bftkv_gpu_batcher_cert_verify", "bftkv_gpu_host_pipeline_trace",
     "bftkv_gpu_batcher_cert_entity", "bftkv_gpu_set_lagrange_x_bound", "bftkv_gpu_batcher_modmul_product", "bftkv_gpu_batcher_lagrange_combine", "bftkv_gpu_batcher_dsa_calculate_r", "bftkv_gpu_batcher_modexp",
     "bftkv_gpu_ecdsa_calculate_r", "bftkv_gpu_ecdsa_calculate_r_dev", "bftkv_gpu_batcher_ecdsa_calculate_r", "bftkv_gpu_ec_scalar_base_mult",
+    "bftkv_gpu_ecdsa_verify", "bftkv_gpu_ecdsa_verify_dev", "bftkv_gpu_batcher_ecdsa_verify",
 ]
 
 _lib = None
@@ -138,6 +139,9 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_ecdsa_calculate_r_dev.argtypes = lib.bftkv_gpu_ecdsa_calculate_r.argtypes
     lib.bftkv_gpu_batcher_ecdsa_calculate_r.argtypes = [vp, u32, vp, u8p, u8p, u8p, u32, u8p, u8p]
     lib.bftkv_gpu_ec_scalar_base_mult.argtypes = [vp, u32, u8p, u32, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_ecdsa_verify.argtypes = [vp, u32, u8p, u32, u8p, vp, u32, u8p, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_ecdsa_verify_dev.argtypes = lib.bftkv_gpu_ecdsa_verify.argtypes
+    lib.bftkv_gpu_batcher_ecdsa_verify.argtypes = [vp, u8p, u32, u8p, u8p, u8p, u32, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -577,6 +581,21 @@ class Context:
         self._check(self.lib.bftkv_gpu_ec_scalar_base_mult(self.h, n, _ptr(sc), f, _ptr(cb), bits, _ptr(out), _ptr(st)), "ec_scalar_base_mult")
         return [out[i].tobytes() for i in range(n)], st[:n]
 
+    def ecdsa_verify(self, digests, sigs, keys, curve, key_idx=None):
+        """crypto/ecdsa.Verify on raw signatures: digests [n_ops] bytes of ONE length (1..66), sigs [n_ops] bytes r || s (2 fbytes
+        each), keys [n_keys] Marshal bytes (1 + 2 fbytes each), key_idx [n_ops] or None (key 0) -> (valid, status), uint8 each."""
+        cb, bits, f = _curve_bytes(curve)
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        if any(len(d) != dlen for d in digests) or any(len(s) != 2 * f for s in sigs) or any(len(k) != 1 + 2 * f for k in keys) or len(sigs) != n:
+            raise ValueError("ecdsa_verify: digests of one length, sigs of 2 fbytes, keys of 1 + 2 fbytes")
+        dg, sg, kk = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs)), _u8(b"".join(bytes(k) for k in keys))
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_ecdsa_verify(self.h, n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki), len(keys), _ptr(kk),
+                                                    _ptr(cb), bits, _ptr(valid), _ptr(st)), "ecdsa_verify")
+        return valid[:n], st[:n]
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -692,6 +711,16 @@ class Batcher:
         out, st = np.full(f, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
         rc = self.lib.bftkv_gpu_batcher_ecdsa_calculate_r(self.h, len(xs), _ptr(x), _ptr(r), _ptr(v), _ptr(cb), bits, _ptr(out), _ptr(st))
         return rc, int(st[0]), int.from_bytes(out.tobytes(), "big")
+
+    def ecdsa_verify(self, digest: bytes, sig: bytes, key: bytes, curve):
+        """crypto/ecdsa.Verify for one raw signature r || s under Marshal bytes `key` -> (rc, status, valid)."""
+        cb, bits, f = _curve_bytes(curve)
+        if len(sig) != 2 * f or len(key) != 1 + 2 * f or not digest:
+            raise ValueError("ecdsa_verify: sig of 2 fbytes, key of 1 + 2 fbytes, a non-empty digest")
+        dg, sg, kk = _u8(digest), _u8(sig), _u8(key)
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_ecdsa_verify(self.h, _ptr(dg), len(digest), _ptr(sg), _ptr(kk), _ptr(cb), bits, _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
 
     def modexp(self, base: int, exp: int, mod: int, nbytes: int = 256, exp_len: int = 32):
         """base^exp mod `mod` (CalculatePartialR dsa.go:27-31; the per-fragment power of rsa.go:161-171)."""

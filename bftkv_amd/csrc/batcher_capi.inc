@@ -301,7 +301,7 @@ struct bftkv_gpu_batcher {
     uint8_t* fname_out = nullptr; uint8_t fname_len = 0;
     // kinds 0 / 1: SHA-256 state after the whole blocks of tbs, absorbed by the caller's own thread in submit()
     uint32_t mid[8] = {};
-    // kinds 4..7: one operation of th_k terms over numbers of th_nbytes (th_qbytes: the order's width for CalculateR, the exponent's
+    // kinds 4..9: one operation of th_k terms over numbers of th_nbytes (th_qbytes: the order's width for CalculateR, the exponent's
     // for kind 7); requests of one SHAPE (kind, k, widths) share a device call, whatever their moduli
     uint64_t th_shape = 0;
     uint32_t th_k = 0, th_nbytes = 0, th_qbytes = 0;
@@ -482,10 +482,38 @@ struct bftkv_gpu_batcher {
     }
   }
 
+  // kind 9: ECDSA verification.  A group's callers share a curve and a digest length (th_k = dlen); th_a = digest, th_b = r || s,
+  // th_mod2 = the key, th_out = the verdict byte.  The distinct keys of the group make the call's key table.
+  void run_ecdsa_verify(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k, f = r0.th_nbytes;
+    const size_t kw = 1 + 2 * (size_t)f;
+    std::map<std::string, uint32_t> slot;
+    std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * f), keys, valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    std::vector<uint32_t> idx(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
+      memcpy(&sg[(size_t)i * 2 * f], g[i]->th_b, 2 * (size_t)f);
+      auto ins = slot.emplace(std::string((const char*)g[i]->th_mod2, kw), (uint32_t)slot.size());
+      if (ins.second) keys.insert(keys.end(), g[i]->th_mod2, g[i]->th_mod2 + kw);
+      idx[i] = ins.first->second;
+    }
+    const int rc = ecdsa_verify_impl(lane.ctx, n, dg.data(), dlen, sg.data(), idx.data(), (uint32_t)slot.size(), keys.data(), r0.th_mod, r0.th_qbytes,
+                                     valid.data(), st.data(), false);
+    ++device_calls;
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(9) : st[i];
+      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
+    }
+  }
+
   void run_threshold(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const int kind = r0.kind;
     if (kind == 8) { run_ecdsa(lane, g, device_calls); return; }
+    if (kind == 9) { run_ecdsa_verify(lane, g, device_calls); return; }
     const uint32_t n = (uint32_t)g.size(), k = r0.th_k, nb = r0.th_nbytes, qb = r0.th_qbytes;
     // (CalculateR: a group (p, q) is one table row)
     std::map<std::string, uint32_t> slot;
@@ -827,6 +855,23 @@ int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const 
   r.th_k = k; r.th_nbytes = f; r.th_qbytes = bit_size; r.th_xs = xs; r.th_a = ri; r.th_b = vi; r.th_mod = curve; r.th_mod2 = nullptr; r.th_out = r_out;
   const int rc = b->submit(r);
   *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
+  return rc;
+}
+
+int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, const uint8_t* key,
+                                   const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (valid_out) *valid_out = 0;
+  if (!b || !status_out || !valid_out || !digest || !sig || !key || !curve || bit_size == 0 || bit_size > 521 || dlen == 0 || dlen > 66)
+    return BFTKV_E_INVALID;
+  if (ec_curve_id(curve, bit_size) < 0) return BFTKV_E_UNSUPPORTED;       // for this caller alone
+  bftkv_gpu_batcher::Req r{9, -4, nullptr, 0, nullptr, 0, false, 0};
+  r.th_shape = (uint64_t)9 | (uint64_t)dlen << 8 | (uint64_t)bit_size << 24;
+  r.th_k = dlen; r.th_nbytes = (bit_size + 7) / 8; r.th_qbytes = bit_size; r.th_a = digest; r.th_b = sig; r.th_mod = curve; r.th_mod2 = key;
+  r.th_out = valid_out;
+  const int rc = b->submit(r);
+  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
+  if (rc) *valid_out = 0;
   return rc;
 }
 

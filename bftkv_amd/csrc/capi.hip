@@ -158,6 +158,9 @@ struct bftkv_gpu_ctx {
   DevBuf chunk_arena, chunk_ctr;    // linearised partial-length signature bodies (parse_one) and their counters (k_walk / k_scan_counts)
   uint32_t multiexp_parts = 0;        // experiment knob (BFTKV_MULTIEXP_PARTS): quads per CalculateR operation, 0 = default policy
   uint32_t ec_split = 0;              // experiment knob (BFTKV_EC_SPLIT): ECDSA CalculateR lanes, 1 = per term, 2 = per operation, 0 = default policy
+  uint32_t ec_window = 0;             // experiment knob (BFTKV_EC_WINDOW = 2..8): window bits of the fixed-base G tables, 0 = the default (4)
+  DevBuf ec_fb_tab[4];                // ECDSA verification: the fixed-base table of G per recognised curve (ec_field.h fb_table_build), built at first use
+  uint32_t ec_fb_w[4] = {};           // ... and its window width (0: not built)
   uint32_t multiexp_block = 0;        // experiment knob (BFTKV_MULTIEXP_BLOCK = 64): one-wave blocks for the 4-lane k_multiexp
   uint32_t multiexp_lanes = 0;        // experiment knob (BFTKV_MULTIEXP_LANES = 4 | 8): lanes per number in k_multiexp, 0 = by call size
   uint32_t dsa_inv_mode = 0;          // experiment knob (BFTKV_DSA_INV = single | batched): 1 / 2, 0 = by batch shape
@@ -1186,6 +1189,7 @@ int bftkv_gpu_init(int device_ordinal, bftkv_gpu_ctx** out) {
   if (const char* e = getenv("BFTKV_MODEXP_LDS_PAD")) c->modexp_lds_pad = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_PARTS")) c->multiexp_parts = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_EC_SPLIT")) c->ec_split = (uint32_t)atoi(e);
+  if (const char* e = getenv("BFTKV_EC_WINDOW")) c->ec_window = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_LANES")) c->multiexp_lanes = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_BLOCK")) c->multiexp_block = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_DSA_INV")) c->dsa_inv_mode = !strcmp(e, "batched") ? 2u : !strcmp(e, "single") ? 1u : 0u;
@@ -1237,6 +1241,7 @@ void bftkv_gpu_destroy(bftkv_gpu_ctx* c) {
   if (c->root) c->root->n_forks.fetch_sub(1);
   for (DevBuf* b : c->scratch_pool) { b->release(); delete b; }
   for (auto& kv : c->modtab_cache) for (DevBuf& b : kv.second) b.release();
+  for (DevBuf& b : c->ec_fb_tab) b.release();
   if (c->h_mail) (void)hipHostFree(c->h_mail);
   if (c->hb_out) (void)hipHostFree(c->hb_out);
   if (c->hb_ring) { if (c->stream_c) (void)hipStreamSynchronize(c->stream_c); delete (HbRing*)c->hb_ring; }

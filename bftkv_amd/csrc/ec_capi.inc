@@ -1,5 +1,6 @@
 // C ABI of the threshold-ECDSA entry points (include/bftkv_gpu.h): CalculateR and CalculatePartialR of
-// crypto/threshold/ecdsa/ecdsa.go over crypto/elliptic's four curves.  Kernels: ec_kernels.hip.
+// crypto/threshold/ecdsa/ecdsa.go over crypto/elliptic's four curves, and crypto/ecdsa.Verify on raw signatures.  Kernels:
+// ec_kernels.hip.
 namespace {
 
 // The groups the library recognises, by value: P, N, B, Gx, Gy (big-endian hex) and BitSize of crypto/elliptic's curves.  The
@@ -166,6 +167,91 @@ int ec_scalar_base_mult_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* sc
   return finish(c, false);
 }
 
+// The fixed-base table of G for curve `id` on this context (ec_field.h fb_table_build), built and uploaded at the curve's first
+// verification and kept until the context goes.  Window width: 4 bits (BFTKV_EC_WINDOW tries others; DESIGN.md section 4).
+template <int L>
+int ec_fb_table(bftkv_gpu_ctx* c, int id, const ecf::Curve<L>& C, const uint32_t** tab, uint32_t* w_out, uint32_t* nwin_out) {
+  const uint32_t w = c->ec_window >= 2 && c->ec_window <= 8 ? c->ec_window : 4;
+  const uint32_t nwin = ecf::fb_windows(C.fbytes, w);
+  if (c->ec_fb_w[id] != w) {
+    std::vector<uint32_t> host(ecf::fb_table_words<L>(w, nwin));
+    ecf::fb_table_build<L>(host.data(), w, nwin, C);
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // (a table of another width may still be read)
+    int rc;
+    if ((rc = upload(c, c->ec_fb_tab[id], host))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));            // the vector dies here
+    c->ec_fb_w[id] = w;
+  }
+  *tab = c->ec_fb_tab[id].as<uint32_t>();
+  *w_out = w;
+  *nwin_out = nwin;
+  return 0;
+}
+
+int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, const uint32_t* key_idx,
+                      uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out, bool dev) {
+  if (!c || !curve || !keys || bit_size == 0 || bit_size > 521 || n_keys == 0 || n_keys > (1u << 24) || dlen == 0 || dlen > 66 || n_ops > (1u << 24) ||
+      (n_ops && (!digests || !sigs || !valid_out || !status_out)))
+    return BFTKV_E_INVALID;
+  const int id = ec_curve_id(curve, bit_size);
+  if (id < 0) return BFTKV_E_UNSUPPORTED;
+  if (n_ops == 0) return 0;
+  const uint32_t f = (bit_size + 7) / 8;
+  ctx_lock lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
+  if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
+  else memset(valid_out, 0, n_ops);
+  ScratchBufs sb(c);
+  { int grc = modtab_gc(c); if (grc) return grc; }
+  ModTab mq;
+  uint32_t *d_gi, *d_ki = nullptr;
+  uint8_t *d_dg, *d_sig, *d_keys;
+  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2, *d_valid, *d_st;
+  if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq))) return rc;                      // N, for k_modinv
+  if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
+  if (key_idx) {                                                                       // clamped on the device, for host callers too
+    uint32_t* raw;
+    if ((rc = to_dev(c, sb, key_idx, n_ops, &raw, dev)) || (rc = idx_to_dev(c, sb, raw, n_ops, n_keys, &d_ki, true))) return rc;
+  }
+  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
+  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * f, &d_sig, dev))) return rc;
+  if ((rc = to_dev(c, sb, keys, (size_t)n_keys * (1 + 2 * f), &d_keys))) return rc;
+  if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
+      (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
+    return rc;
+  if (dev) { d_valid = valid_out; d_st = status_out; }
+  else if ((rc = dev_alloc(c, sb, n_ops, &d_valid, false)) || (rc = dev_alloc(c, sb, n_ops, &d_st, false))) return rc;
+  hipStream_t s = c->stream;
+  ec_dispatch(id, curve, [&](auto C) {
+    constexpr int L = decltype(C)::kWords;
+    const uint32_t* tab;
+    uint32_t w, nwin;
+    if ((rc = ec_fb_table<L>(c, id, C, &tab, &w, &nwin))) return;
+    if ((rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_u2, false)) ||
+        (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_r, false)) ||
+        (rc = dev_alloc(c, sb, (size_t)n_ops * 3 * L * 4, &d_pt, false)))
+      return;
+    const dim3 grid((n_ops + EC_BLOCK - 1) / EC_BLOCK), block(EC_BLOCK);
+    hipLaunchKernelGGL(k_ecv_prep<L>, grid, block, 0, s, n_ops, (const uint8_t*)d_dg, dlen, bit_size, (const uint8_t*)d_sig, C, (uint32_t*)d_s28,
+                       (uint32_t*)d_e, (uint32_t*)d_r, (uint8_t*)d_flag);
+    // w = s^-1 mod N: the general inverse (N reaches 521 bits), as in CalculateR
+    hipLaunchKernelGGL(k_modinv, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint32_t*)d_s28, (const uint32_t*)d_gi, mq, (uint32_t*)d_w28,
+                       (uint8_t*)d_ibad, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+    hipLaunchKernelGGL(k_ecv_base<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint32_t*)d_e, (const uint32_t*)d_w28,
+                       (const uint8_t*)d_flag, C, tab, w, nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
+    hipLaunchKernelGGL(k_ecv_key<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint8_t*)d_keys, (const uint32_t*)d_ki, n_keys,
+                       (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag, (const uint8_t*)d_ibad, C, (uint8_t*)d_valid, (uint8_t*)d_st);
+  });
+  if (rc) return rc;
+  if (!dev) {
+    HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
+  }
+  return finish(c, dev);
+}
+
 }  // namespace
 
 extern "C" {
@@ -181,6 +267,15 @@ int bftkv_gpu_ecdsa_calculate_r_dev(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k
 int bftkv_gpu_ec_scalar_base_mult(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* scalars, uint32_t sbytes, const uint8_t* curve,
                                   uint32_t bit_size, uint8_t* out, uint8_t* status_out) {
   return ec_scalar_base_mult_impl(c, n_ops, scalars, sbytes, curve, bit_size, out, status_out);
+}
+
+int bftkv_gpu_ecdsa_verify(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, const uint32_t* key_idx,
+                           uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out) {
+  return ecdsa_verify_impl(c, n_ops, digests, dlen, sigs, key_idx, n_keys, keys, curve, bit_size, valid_out, status_out, false);
+}
+int bftkv_gpu_ecdsa_verify_dev(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, const uint32_t* key_idx,
+                               uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out) {
+  return ecdsa_verify_impl(c, n_ops, digests, dlen, sigs, key_idx, n_keys, keys, curve, bit_size, valid_out, status_out, true);
 }
 
 }  // extern "C"

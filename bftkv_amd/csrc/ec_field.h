@@ -7,7 +7,9 @@
 // representation makes "is zero" and "equal" plain word compares -- what the exceptional cases of point addition need.
 // Points are Jacobian (X : Y : Z), Z = 0 is the point at infinity.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <vector>
 
 #ifndef EC_HD
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -258,6 +260,47 @@ EC_HD void pt_mul(Jac<L>& R, const Jac<L>& P, const uint32_t* k, const Curve<L>&
   R = acc;
 }
 
+// P + (qx, qy) for a finite affine point in Montgomery form (Z2 = 1): pt_add without the three products that Z2 costs, 8
+// products and 3 squarings.  Exact for every input and the same case codes as pt_add.  R may alias P.  Every exit writes R.y
+// last, as pt_dbl does: with exits that end on different words the compiler merges the final stores behind a pointer into
+// private memory, and the table walk that inlines this gets 12 bytes of scratch.
+template <int L>
+EC_HD int pt_add_affine(Jac<L>& R, const Jac<L>& P, const uint32_t* qx, const uint32_t* qy, const Curve<L>& C) {
+  if (pt_is_inf<L>(P)) {
+    fe_copy<L>(R.z, C.one);
+    fe_copy<L>(R.x, qx);
+    fe_copy<L>(R.y, qy);
+    return EC_ADD_INF_OPERAND;
+  }
+  uint32_t h[L], rr[L], t[L], v[L];
+  fp_sqr<L>(t, P.z, C);
+  fp_mul<L>(h, qx, t, C);                               // U2 = X2 Z1^2
+  fp_sub<L>(h, h, P.x, C);                              // H = U2 - X1
+  fp_mul<L>(t, t, P.z, C);
+  fp_mul<L>(rr, qy, t, C);                              // S2 = Y2 Z1^3
+  fp_sub<L>(rr, rr, P.y, C);                            // r = S2 - Y1
+  if (fe_is_zero<L>(h)) {
+    if (fe_is_zero<L>(rr)) { pt_dbl<L>(R, P, C); return EC_ADD_EQUAL; }
+    fe_zero<L>(R.z);
+    fe_zero<L>(R.x);
+    fe_zero<L>(R.y);
+    return EC_ADD_OPPOSITE;
+  }
+  fp_mul<L>(R.z, P.z, h, C);                            // Z3 = Z1 H
+  fp_sqr<L>(t, h, C);                                   // H^2
+  fp_mul<L>(v, P.x, t, C);                              // V = X1 H^2
+  fp_mul<L>(h, h, t, C);                                // H^3
+  fp_sqr<L>(t, rr, C);
+  fp_sub<L>(t, t, h, C);
+  fp_sub<L>(t, t, v, C);
+  fp_sub<L>(R.x, t, v, C);                              // X3 = r^2 - H^3 - 2 V
+  fp_mul<L>(h, P.y, h, C);                              // Y1 H^3
+  fp_sub<L>(t, v, R.x, C);
+  fp_mul<L>(t, rr, t, C);
+  fp_sub<L>(R.y, t, h, C);                              // Y3 = r (V - X3) - Y1 H^3
+  return EC_ADD_GENERAL;
+}
+
 // affine coordinates, plain (out of Montgomery form); infinity -> (0, 0) as Go's affineFromJacobian
 template <int L>
 EC_HD void pt_affine(uint32_t* x, uint32_t* y, const Jac<L>& P, const Curve<L>& C) {
@@ -300,6 +343,70 @@ EC_HD void fn_mul(uint32_t* r, const uint32_t* a, const uint32_t* b, const Curve
   fe_mul<L>(r, t, C.rr_n, C.n, C.n0inv);
 }
 
+// ---- ECDSA verification (crypto/ecdsa.Verify of Go 1.13) ----------------------------------------------------------------
+// hashToInt, then mod N: the leftmost fbytes bytes of a longer digest, shifted right by the bits beyond the order's length
+// (bits = N.BitLen(), the curve's bit size on all four curves); a shorter digest whole.  e < 2^bits <= 2N before the subtraction.
+template <int L>
+EC_HD void hash_to_int(uint32_t* e, const uint8_t* dg, uint32_t dlen, uint32_t bits, const Curve<L>& C) {
+  const uint32_t take = dlen > C.fbytes ? C.fbytes : dlen;
+  fe_from_be<L>(e, dg, take);
+  if (8u * take > bits) {
+    const uint32_t sh = 8u * take - bits;                // 7 on P-521, nothing elsewhere
+#pragma unroll
+    for (int i = 0; i < L; ++i) e[i] = (e[i] >> sh) | (i + 1 < L ? e[i + 1] << (32u - sh) : 0u);
+  }
+  if (!fe_lt<L>(e, C.n)) fe_sub<L>(e, e, C.n, C.n);      // (e - N >= 0: no add-back)
+}
+
+// x(R) mod N == r for a finite R and 0 < r < N, without leaving Jacobian coordinates: x = X / Z^2 < p < 2N is r or r + N, so
+// X == r Z^2 or, where r + N < p, X == (r + N) Z^2 (mod p).
+template <int L>
+EC_HD bool x_matches_r(const Jac<L>& R, const uint32_t* r, const Curve<L>& C) {
+  uint32_t z2[L], t[L], u[L];
+  fp_sqr<L>(z2, R.z, C);
+  fp_mul<L>(t, r, C.rr_p, C);                             // (r < N < p)
+  fp_mul<L>(t, t, z2, C);
+  if (fe_eq<L>(t, R.x)) return true;
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < L; ++i) { c += (uint64_t)r[i] + C.n[i]; u[i] = (uint32_t)c; c >>= 32; }
+  if (c || !fe_lt<L>(u, C.p)) return false;
+  fp_mul<L>(t, u, C.rr_p, C);
+  fp_mul<L>(t, t, z2, C);
+  return fe_eq<L>(t, R.x);
+}
+
+// The fixed-base table of a curve: the affine points j 2^(w i) G in Montgomery form, windows i = 0 .. nwin - 1 of w bits (nwin w
+// covers the scalar), digits j = 1 .. 2^w - 1.  Word-major inside a window: word k (k < L: x, k >= L: y) of digit j is
+//   tab[((i 2L + k) << w) + j]       (slot j = 0 unused, zero)
+// so the 64 lanes of a wave, which walk the same window with their own digits, read one word of their entries from one 2^w-word
+// run (64 bytes at w = 4: one line per load instruction, whatever the digits).
+EC_HD uint32_t fb_windows(uint32_t fbytes, uint32_t w) { return (8u * fbytes + w - 1u) / w; }
+template <int L>
+EC_HD size_t fb_table_words(uint32_t w, uint32_t nwin) { return ((size_t)nwin * 2 * L) << w; }
+
+// k G for k < 2^(w nwin) (L words) from the table: one mixed addition per non-zero digit, no doubling.  The digits come off a
+// copy of k that is shifted down, so that no register array is indexed by a variable.
+template <int L>
+EC_HD void fb_mul(Jac<L>& R, const uint32_t* tab, uint32_t w, uint32_t nwin, const uint32_t* k, const Curve<L>& C) {
+  uint32_t kw[L], qx[L], qy[L];
+  fe_copy<L>(kw, k);
+  Jac<L> acc;
+  pt_set_inf<L>(acc);
+  const uint32_t mask = (1u << w) - 1u;
+  for (uint32_t i = 0; i < nwin; ++i) {
+    const uint32_t d = kw[0] & mask;
+#pragma unroll
+    for (int j = 0; j < L; ++j) kw[j] = (kw[j] >> w) | (j + 1 < L ? kw[j + 1] << (32u - w) : 0u);
+    if (d == 0) continue;
+    const uint32_t* e = tab + (((size_t)i * 2 * L) << w) + d;
+#pragma unroll
+    for (int j = 0; j < L; ++j) { qx[j] = e[(size_t)j << w]; qy[j] = e[(size_t)(L + j) << w]; }
+    pt_add_affine<L>(acc, acc, qx, qy, C);
+  }
+  R = acc;
+}
+
 // ---- constants, on the host (once per curve and context) -------------------------------------------------------------
 EC_HD uint32_t neg_inv32(uint32_t m0) {      // -m0^-1 mod 2^32 (m0 odd), Newton
   uint32_t x = m0;
@@ -335,6 +442,44 @@ EC_HD void curve_setup(Curve<L>& C, const uint8_t* be, uint32_t fbytes) {
   fp_mul<L>(C.gy, g, C.rr_p, C);
   uint64_t br = 2;
   for (int i = 0; i < L; ++i) { const uint64_t v = (uint64_t)C.p[i] - br; C.pm2[i] = (uint32_t)v; br = v >> 63; }
+}
+
+// The fixed-base table of fb_mul (tab: fb_table_words<L>(w, nwin) words), host only.  Window i's points are sums of
+// B_i = 2^(w i) G through the exact pt_add; all of them are made affine with ONE field inversion (Montgomery's trick: no
+// j 2^(w i) is a multiple of the prime N > 2^w, so every Z is non-zero).
+template <int L>
+inline void fb_table_build(uint32_t* tab, uint32_t w, uint32_t nwin, const Curve<L>& C) {
+  const uint32_t per = (1u << w) - 1u;
+  const size_t n = (size_t)nwin * per;
+  std::vector<Jac<L>> pts(n);
+  std::vector<uint32_t> pre(n * L);
+  Jac<L> base;
+  fe_copy<L>(base.x, C.gx);
+  fe_copy<L>(base.y, C.gy);
+  fe_copy<L>(base.z, C.one);
+  for (uint32_t i = 0; i < nwin; ++i) {
+    Jac<L>* row = &pts[(size_t)i * per];
+    row[0] = base;
+    for (uint32_t j = 1; j < per; ++j) pt_add<L>(row[j], row[j - 1], base, C);
+    for (uint32_t b = 0; b < w; ++b) pt_dbl<L>(base, base, C);
+  }
+  for (size_t i = 0; i < n; ++i) {                        // pre[i] = Z_0 ... Z_i
+    if (i == 0) fe_copy<L>(&pre[0], pts[0].z);
+    else fp_mul<L>(&pre[i * L], &pre[(i - 1) * L], pts[i].z, C);
+  }
+  uint32_t inv[L], zi[L], z2[L];
+  fp_inv<L>(inv, &pre[(n - 1) * L], C);
+  for (size_t k = 0; k < fb_table_words<L>(w, nwin); ++k) tab[k] = 0;
+  for (size_t i = n; i-- > 0;) {
+    if (i) { fp_mul<L>(zi, inv, &pre[(i - 1) * L], C); fp_mul<L>(inv, inv, pts[i].z, C); }
+    else fe_copy<L>(zi, inv);
+    fp_sqr<L>(z2, zi, C);
+    fp_mul<L>(pts[i].x, pts[i].x, z2, C);
+    fp_mul<L>(z2, z2, zi, C);
+    fp_mul<L>(pts[i].y, pts[i].y, z2, C);
+    uint32_t* e = tab + (((size_t)(i / per) * 2 * L) << w) + (i % per + 1);
+    for (int k = 0; k < L; ++k) { e[(size_t)k << w] = pts[i].x[k]; e[(size_t)(L + k) << w] = pts[i].y[k]; }
+  }
 }
 
 }  // namespace ecf

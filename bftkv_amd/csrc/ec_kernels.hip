@@ -4,6 +4,7 @@
 //   k_ec_fold       thread / operation: S = T_0 + ... + T_(k-1) in j order with the fence rules, r = x(S) mod N
 //   k_ec_calc_r_op  thread / operation: both of the above in one lane (the split for calls with many terms per SIMD)
 //   k_ec_base_mult  thread / scalar: Marshal(s G)                                                             CalculatePartialR
+//   k_ecv_prep / k_ecv_base / k_ecv_key   thread / signature: ecdsa.Verify on raw r || s (further down)        Verify
 // w = v^-1 mod N is folded into the per-term scalars: the curves have prime order, so sum (l_j w) R_j = w sum l_j R_j and
 // the scaled prefix sums meet +-T_j and infinity exactly where the reference's unscaled ones do.
 // Status bytes: bit 2 = fenced (the reference decides), bit 1 = v has no inverse (k_modinv's); copy_status normalises.
@@ -186,6 +187,110 @@ __global__ void __launch_bounds__(EC_BLOCK) k_ec_base_mult(uint32_t n_ops, const
   ecf::fe_to_be<L>(o + 1, f, x);
   ecf::fe_to_be<L>(o + 1 + f, f, y);
   status[op] = BFTKV_TH_OK;
+}
+
+// ---- ECDSA verification (crypto/ecdsa.Verify, Go 1.13): a thread per signature in three kernels around k_modinv -------------
+//   k_ecv_prep   range checks on r and s, e = hashToInt(digest) mod N, r and e as words, s as radix-2^28 limbs for k_modinv
+//   k_ecv_base   u1 = e w, u2 = r w mod N, u1 G from the curve's fixed-base table (fb_mul)          -> HBM
+//   k_ecv_key    Unmarshal's checks on the key, u2 Q (pt_mul), ONE pt_add of the two multiples, the x comparison, the verdict
+// The two multiples stay separate points until that last addition: its case code is the fence (u1 G = u2 Q is Add's doubling
+// case) and the INVALID of a sum at infinity.  They meet through HBM because a P-521 lane cannot hold the finished u1 G (51
+// words) beside pt_mul's working set without scratch.
+// flag byte of an operation: 0 go on, 1 decided INVALID (r or s outside [1, N)), 2 fenced (e = 0 mod N)
+enum { ECV_GO = 0, ECV_INVALID = 1, ECV_FENCED = 2 };
+
+template <int L>
+__device__ __forceinline__ void ec_to_limbs28(uint32_t* lim, const uint32_t* w) {
+#pragma unroll
+  for (int k = 0; k < MONT_N; ++k) {
+    const int bit = 28 * k, wi = bit >> 5, sh = bit & 31;
+    uint32_t v = 0;
+    if (wi < L) v = w[wi] >> sh;
+    if (sh > 4 && wi + 1 < L) v |= w[wi + 1] << (32 - sh);
+    lim[k] = v & 0x0FFFFFFFu;
+  }
+}
+
+template <int L>
+__global__ void __launch_bounds__(EC_BLOCK) k_ecv_prep(uint32_t n_ops, const uint8_t* __restrict__ digests /*[n_ops][dlen]*/, uint32_t dlen, uint32_t bits,
+                                                       const uint8_t* __restrict__ sigs /*[n_ops][2 f]*/, ecf::Curve<L> C,
+                                                       uint32_t* __restrict__ s28 /*[n_ops][76]*/, uint32_t* __restrict__ e_out /*[n_ops][L]*/,
+                                                       uint32_t* __restrict__ r_out /*[n_ops][L]*/, uint8_t* __restrict__ flag) {
+  const uint32_t op = blockIdx.x * blockDim.x + threadIdx.x;
+  if (op >= n_ops) return;
+  const uint32_t f = C.fbytes;
+  uint32_t r[L], s[L], e[L];
+  ecf::fe_from_be<L>(r, sigs + (uint64_t)op * 2 * f, f);
+  ecf::fe_from_be<L>(s, sigs + (uint64_t)op * 2 * f + f, f);
+  ecf::hash_to_int<L>(e, digests + (uint64_t)op * dlen, dlen, bits, C);
+  uint8_t fl = ECV_GO;
+  if (ecf::fe_is_zero<L>(r) || ecf::fe_is_zero<L>(s) || !ecf::fe_lt<L>(r, C.n) || !ecf::fe_lt<L>(s, C.n)) fl = ECV_INVALID;
+  else if (ecf::fe_is_zero<L>(e)) fl = ECV_FENCED;         // u1 = 0: the affine (0, 0) would go into Add
+  if (fl) { ecf::fe_zero<L>(s); s[0] = 1; }               // (k_modinv still runs on the lane: give it an invertible number)
+  ec_to_limbs28<L>(s28 + (uint64_t)op * MONT_N, s);
+#pragma unroll
+  for (int i = 0; i < L; ++i) { e_out[(uint64_t)op * L + i] = e[i]; r_out[(uint64_t)op * L + i] = r[i]; }
+  flag[op] = fl;
+}
+
+template <int L>
+__global__ void __launch_bounds__(EC_BLOCK) k_ecv_base(uint32_t n_ops, const uint32_t* __restrict__ r_in, const uint32_t* __restrict__ e_in,
+                                                       const uint32_t* __restrict__ winv28, const uint8_t* __restrict__ flag, ecf::Curve<L> C,
+                                                       const uint32_t* __restrict__ tab, uint32_t w, uint32_t nwin,
+                                                       uint32_t* __restrict__ pt_out /*[n_ops][3 L]*/, uint32_t* __restrict__ u2_out /*[n_ops][L]*/) {
+  const uint32_t op = blockIdx.x * blockDim.x + threadIdx.x;
+  if (op >= n_ops || flag[op]) return;
+  uint32_t wv[L], u[L], t[L];
+  ec_from_limbs28<L>(wv, winv28 + (uint64_t)op * MONT_N);
+#pragma unroll
+  for (int i = 0; i < L; ++i) t[i] = r_in[(uint64_t)op * L + i];
+  ecf::fn_mul<L>(u, t, wv, C);                              // u2 = r w
+#pragma unroll
+  for (int i = 0; i < L; ++i) u2_out[(uint64_t)op * L + i] = u[i];
+#pragma unroll
+  for (int i = 0; i < L; ++i) t[i] = e_in[(uint64_t)op * L + i];
+  ecf::fn_mul<L>(u, t, wv, C);                              // u1 = e w  (not 0: e != 0 and N is prime)
+  ecf::Jac<L> P;
+  ecf::fb_mul<L>(P, tab, w, nwin, u, C);
+  ec_store_jac<L>(pt_out + (uint64_t)op * 3 * L, P);
+}
+
+// (inv_bad: k_modinv's byte array, set only if s had no inverse -- N is prime, so never; such an operation stays BFTKV_TH_FAILED)
+template <int L>
+__global__ void __launch_bounds__(EC_BLOCK) k_ecv_key(uint32_t n_ops, const uint32_t* __restrict__ r_in, const uint8_t* __restrict__ keys /*[n_keys][1 + 2 f]*/,
+                                                      const uint32_t* __restrict__ key_idx, uint32_t n_keys, const uint32_t* __restrict__ u2_in,
+                                                      const uint32_t* __restrict__ pt_in, const uint8_t* __restrict__ flag,
+                                                      const uint8_t* __restrict__ inv_bad, ecf::Curve<L> C, uint8_t* __restrict__ valid_out,
+                                                      uint8_t* __restrict__ status_out) {
+  const uint32_t op = blockIdx.x * blockDim.x + threadIdx.x;
+  if (op >= n_ops) return;
+  const uint32_t f = C.fbytes;
+  const uint8_t* kb = keys + (uint64_t)(key_idx ? min(key_idx[op], n_keys - 1u) : 0u) * (1 + 2 * f);
+  uint8_t valid = 0, st = BFTKV_TH_OK;
+  const uint8_t fl = flag[op];
+  uint32_t x[L], y[L];
+  ecf::Jac<L> Q, A;
+  ecf::fe_from_be<L>(x, kb + 1, f);
+  ecf::fe_from_be<L>(y, kb + 1 + f, f);
+  if (kb[0] != 4 || !ecf::pt_check<L>(Q.x, Q.y, x, y, C)) st = BFTKV_TH_FENCED;       // no reference key object holds this point
+  else if (fl == ECV_FENCED) st = BFTKV_TH_FENCED;
+  else if (inv_bad[op]) st = BFTKV_TH_FAILED;
+  else if (fl == ECV_GO) {
+    ecf::fe_copy<L>(Q.z, C.one);
+#pragma unroll
+    for (int i = 0; i < L; ++i) x[i] = u2_in[(uint64_t)op * L + i];
+    ecf::pt_mul<L>(A, Q, x, C);                              // u2 Q: finite (0 < u2 < N, prime order)
+    ec_load_jac<L>(Q, pt_in + (uint64_t)op * 3 * L);         // u1 G
+    const int code = ecf::pt_add<L>(A, Q, A, C);
+    if (code == ecf::EC_ADD_EQUAL) st = BFTKV_TH_FENCED;     // Add's doubling case on the generic path
+    else if (code == ecf::EC_ADD_GENERAL) {                  // (opposite: the sum is infinity, INVALID)
+#pragma unroll
+      for (int i = 0; i < L; ++i) x[i] = r_in[(uint64_t)op * L + i];
+      valid = ecf::x_matches_r<L>(A, x, C) ? 1 : 0;
+    }
+  }
+  valid_out[op] = valid;
+  status_out[op] = st;
 }
 
 }  // namespace bftkv

@@ -385,6 +385,13 @@ int bftkv_gpu_batcher_modexp(bftkv_gpu_batcher* b, const uint8_t* base, uint32_t
  * alone, and a caller's fenced operation fences no one else's. */
 int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
                                         const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out);
+/* crypto/ecdsa.Verify (Go 1.13; the reference calls it as ecdsa.Verify(&priv.PublicKey, dgst, r, s), protocol/dist_test.go:98-102 and
+ * crypto/threshold/ecdsa/ecdsa_test.go:169) for ONE signature: digest [dlen], sig [2 fbytes], key [1 + 2 fbytes], *valid_out and
+ * *status_out as for bftkv_gpu_ecdsa_verify.  Callers on different curves (or with different digest lengths) may share a batcher;
+ * an unrecognised group returns BFTKV_E_UNSUPPORTED for that caller alone, and a caller's fenced or invalid signature changes no
+ * one else's verdict. */
+int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, const uint8_t* key,
+                                   const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -541,6 +548,28 @@ int bftkv_gpu_ecdsa_calculate_r_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, uint32_t
  * comes from the reference (a share mod N): BFTKV_TH_FENCED and zeroes.  status_out [n_ops] as above. */
 int bftkv_gpu_ec_scalar_base_mult(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* scalars, uint32_t sbytes, const uint8_t* curve,
                                   uint32_t bit_size, uint8_t* out, uint8_t* status_out);
+/* crypto/ecdsa.Verify of Go 1.13 on raw signatures -- what the reference asks of a finished threshold signature,
+ * ecdsa.Verify(&priv.PublicKey, dgst, r, s) (protocol/dist_test.go:98-102, crypto/threshold/ecdsa/ecdsa_test.go:169) -- n_ops at once:
+ *   digests [n_ops][dlen], 1 <= dlen <= 66: e = hashToInt (the reference's copy: OS2I, ecdsa.go:88-98): the leftmost fbytes bytes of
+ *           a longer digest, shifted right by the bits beyond N's length (7 on P-521); a shorter digest whole;
+ *   sigs    [n_ops][2 fbytes]: r || s big-endian, as formatDSA writes them (crypto/threshold/dsa/dsa_core.go:375-387);
+ *   keys    [n_keys][1 + 2 fbytes]: elliptic.Marshal bytes 04 || X || Y (n_keys >= 1); key_idx [n_ops] picks one per signature, NULL
+ *           means key 0 for all, an index past the table is clamped to the last key;
+ *   valid_out [n_ops]: 1 where Verify returns true, else 0 (r or s outside [1, N), x(u1 G + u2 Q) mod N != r, or the sum at infinity);
+ *   status_out [n_ops]: BFTKV_TH_OK (valid_out is Verify's answer);
+ *           BFTKV_TH_FENCED (valid_out 0, the reference decides): a key that elliptic.Unmarshal refuses (prefix, coordinates below P,
+ *           on the curve -- no PublicKey holds such a point; this comes before every other rule), e = 0 mod N (the affine (0, 0)
+ *           goes into Add), u1 G = u2 Q (Add's doubling case on the generic path) -- docs/parity.md, "ECDSA verification";
+ *           BFTKV_TH_FAILED whenever the return code is not 0 (the bytes start out as failures, valid_out as 0).
+ * curve, bit_size and BFTKV_E_UNSUPPORTED as for bftkv_gpu_ecdsa_calculate_r; n_ops = 0 returns 0. */
+int bftkv_gpu_ecdsa_verify(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                           const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size,
+                           uint8_t* valid_out, uint8_t* status_out);
+/* same with digests / sigs / key_idx / valid_out / status_out resident in HBM, asynchronous on the context's stream (keys and
+ * curve stay host pointers, read before the call returns). */
+int bftkv_gpu_ecdsa_verify_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                               const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size,
+                               uint8_t* valid_out, uint8_t* status_out);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

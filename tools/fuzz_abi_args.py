@@ -209,6 +209,39 @@ def ecdsa_calls():
         note("batcher_ecdsa_calculate_r", rc)
 
 
+def ecdsa_verify_calls():
+    """bftkv_gpu_ecdsa_verify, its _dev form (whose arrays must live in HBM: only with arguments that are refused, or no
+    operations) and the batcher entry: whatever comes back, a non-zero return leaves failures and no verdict."""
+    bits = rng.choice([0, 1, 8, 224, 255, 256, 384, 521, 522, 4096])
+    f = (bits + 7) // 8
+    n_ops = rng.choice([0, 0, 1, 2, 5, 64])
+    n_keys = rng.choice([0, 1, 1, 2, 7])
+    dlen = rng.choice([0, 1, 20, 32, 48, 64, 66, 67, 4096])
+    cb = ec_curve(bits) if rng.random() < 0.95 else None
+    cbp = p8(cb) if cb is not None else None
+    dg, sg, keys = buf(n_ops * min(dlen, 4096)), buf(n_ops * 2 * f), buf(max(n_keys, 1) * (1 + 2 * f))
+    ki = np.array([rng.choice([0, 1, n_keys, 2 ** 32 - 1]) for _ in range(max(n_ops, 1))], dtype=np.uint32)
+    kip = ki.ctypes.data_as(vp) if rng.random() < 0.5 else None
+    valid, st = buf(n_ops, "zero"), buf(n_ops, "zero")
+    which = rng.randrange(3)
+    if which == 0:
+        rc = lib.bftkv_gpu_ecdsa_verify(ctx, n_ops, p8(dg), dlen, p8(sg), kip, n_keys, p8(keys), cbp, bits, p8(valid), p8(st))
+        assert rc == 0 or not valid[:n_ops].any(), ("ecdsa_verify", rc)
+        note("ecdsa_verify", rc)
+    elif which == 1:
+        if rng.random() < 0.5:
+            n_ops = 0
+        else:
+            dlen = rng.choice([0, 67, 4096])
+        note("ecdsa_verify_dev", lib.bftkv_gpu_ecdsa_verify_dev(ctx, n_ops, p8(dg), dlen, p8(sg), kip, n_keys, p8(keys), cbp, bits, p8(valid), p8(st)))
+    else:
+        v1, s1 = C.c_uint8(0x55), C.c_uint8(0x55)
+        rc = lib.bftkv_gpu_batcher_ecdsa_verify(batcher, p8(buf(min(dlen, 4096))), dlen, p8(buf(2 * f)), p8(buf(1 + 2 * f)), cbp, bits, C.byref(v1),
+                                                C.byref(s1))
+        assert rc == 0 or (s1.value == 0xFF and v1.value == 0), ("batcher_ecdsa_verify", rc, s1.value, v1.value)      # fail closed
+        note("batcher_ecdsa_verify", rc)
+
+
 def offsets(n, total):
     o = np.zeros(n + 1, dtype=np.uint64)
     style = rng.random()
@@ -364,7 +397,7 @@ t0 = time.time()
 n = 0
 while time.time() - t0 < budget:
     rng.choice([threshold_batched, threshold_batched, threshold_one, verify_calls, verify_calls, keyring_and_quorum, cert_calls, cert_calls,
-                ecdsa_calls])()
+                ecdsa_calls, ecdsa_verify_calls])()
     n += 1
 lib.bftkv_gpu_batcher_destroy(batcher)
 lib.bftkv_gpu_destroy(ctx)

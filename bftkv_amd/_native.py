@@ -49,6 +49,8 @@ EXPORTS = [
     "bftkv_gpu_batcher_cert_entity", "bftkv_gpu_set_lagrange_x_bound", "bftkv_gpu_batcher_modmul_product", "bftkv_gpu_batcher_lagrange_combine", "bftkv_gpu_batcher_dsa_calculate_r", "bftkv_gpu_batcher_modexp",
     "bftkv_gpu_ecdsa_calculate_r", "bftkv_gpu_ecdsa_calculate_r_dev", "bftkv_gpu_batcher_ecdsa_calculate_r", "bftkv_gpu_ec_scalar_base_mult",
     "bftkv_gpu_ecdsa_verify", "bftkv_gpu_ecdsa_verify_dev", "bftkv_gpu_batcher_ecdsa_verify",
+    "bftkv_gpu_ecdsa_keyset_create", "bftkv_gpu_ecdsa_keyset_destroy", "bftkv_gpu_ecdsa_keyset_info", "bftkv_gpu_ecdsa_verify_keyset",
+    "bftkv_gpu_ecdsa_verify_keyset_dev", "bftkv_gpu_batcher_ecdsa_verify_keyset", "bftkv_gpu_selftest_ecdsa_keyset_table",
 ]
 
 _lib = None
@@ -142,6 +144,13 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_ecdsa_verify.argtypes = [vp, u32, u8p, u32, u8p, vp, u32, u8p, u8p, u32, u8p, u8p]
     lib.bftkv_gpu_ecdsa_verify_dev.argtypes = lib.bftkv_gpu_ecdsa_verify.argtypes
     lib.bftkv_gpu_batcher_ecdsa_verify.argtypes = [vp, u8p, u32, u8p, u8p, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_ecdsa_keyset_create.argtypes = [vp, u32, u8p, u8p, u32, C.POINTER(C.c_int)]
+    lib.bftkv_gpu_ecdsa_keyset_destroy.argtypes = [vp, C.c_int]
+    lib.bftkv_gpu_ecdsa_keyset_info.argtypes = [vp, C.c_int, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64)]
+    lib.bftkv_gpu_ecdsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, vp, u8p, u8p]
+    lib.bftkv_gpu_ecdsa_verify_keyset_dev.argtypes = lib.bftkv_gpu_ecdsa_verify_keyset.argtypes
+    lib.bftkv_gpu_batcher_ecdsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, u8p, u8p]
+    lib.bftkv_gpu_selftest_ecdsa_keyset_table.argtypes = [vp, C.c_int, u32, vp, C.c_uint64]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -596,6 +605,67 @@ class Context:
                                                     _ptr(cb), bits, _ptr(valid), _ptr(st)), "ecdsa_verify")
         return valid[:n], st[:n]
 
+    def ecdsa_keyset_create(self, keys, curve) -> int:
+        """Register keys [n_keys] Marshal bytes (1 + 2 fbytes each) once: Unmarshal's checks and a table per key on the device.
+        A refused key does not refuse the set (ecdsa_keyset_info counts it; its signatures are fenced)."""
+        cb, bits, f = _curve_bytes(curve)
+        if any(len(k) != 1 + 2 * f for k in keys):
+            raise ValueError("ecdsa_keyset_create: keys of 1 + 2 fbytes")
+        kk = _u8(b"".join(bytes(k) for k in keys))
+        h = C.c_int(-1)
+        self._check(self.lib.bftkv_gpu_ecdsa_keyset_create(self.h, len(keys), _ptr(kk), _ptr(cb), bits, C.byref(h)), "ecdsa_keyset_create")
+        self._keyset_fbytes_cache()[h.value] = f
+        return h.value
+
+    def ecdsa_keyset_destroy(self, keyset: int):
+        self._check(self.lib.bftkv_gpu_ecdsa_keyset_destroy(self.h, keyset), "ecdsa_keyset_destroy")
+        self._keyset_fbytes_cache().pop(keyset, None)
+
+    def ecdsa_keyset_info(self, keyset: int):
+        """-> {n_keys, n_refused, window_bits, table_bytes}"""
+        nk, nr, w, tb = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self.lib.bftkv_gpu_ecdsa_keyset_info(self.h, keyset, C.byref(nk), C.byref(nr), C.byref(w), C.byref(tb)), "ecdsa_keyset_info")
+        return {"n_keys": nk.value, "n_refused": nr.value, "window_bits": w.value, "table_bytes": tb.value}
+
+    def _keyset_fbytes_cache(self):
+        """handle -> coordinate length of the set's curve; one dictionary on the root, which its forks share"""
+        ctx = self
+        while getattr(ctx, "root", None) is not None:
+            ctx = ctx.root
+        return ctx.__dict__.setdefault("_keyset_fbytes", {})
+
+    def _ecdsa_keyset_fbytes(self, keyset: int) -> int:
+        """The coordinate length of a set's curve, as ecdsa_keyset_create recorded it.  A handle that was made through the C entry
+        itself is looked up once, from the size of its tables (windows x 2 L x 2^w words per key); ecdsa_keyset_destroy forgets it."""
+        cache = self._keyset_fbytes_cache()
+        if keyset not in cache:
+            info = self.ecdsa_keyset_info(keyset)
+            w, words = info["window_bits"], info["table_bytes"] // (4 * info["n_keys"])
+            cache[keyset] = next(f for f, nw in ((28, 7), (32, 8), (48, 12), (66, 17)) if (((8 * f + w - 1) // w * 2 * nw) << w) == words)
+        return cache[keyset]
+
+    def ecdsa_verify_keyset(self, keyset: int, digests, sigs, key_idx=None):
+        """ecdsa_verify under the keys of a set: digests [n_ops] bytes of ONE length, sigs [n_ops] bytes r || s of the set's curve,
+        key_idx [n_ops] into the set or None (key 0) -> (valid, status), uint8 each."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        slen = 2 * self._ecdsa_keyset_fbytes(keyset)
+        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or len(sigs) != n:
+            raise ValueError("ecdsa_verify_keyset: digests of one length, sigs of 2 fbytes")
+        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_ecdsa_verify_keyset(self.h, keyset, n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki),
+                                                           _ptr(valid), _ptr(st)), "ecdsa_verify_keyset")
+        return valid[:n], st[:n]
+
+    def selftest_ecdsa_keyset_table(self, keyset: int, key: int) -> np.ndarray:
+        """One key's table as the device built it (uint32 words, the layout of ec_field.h fb_table_build)."""
+        info = self.ecdsa_keyset_info(keyset)
+        words = np.zeros(info["table_bytes"] // (4 * info["n_keys"]), dtype=np.uint32)
+        self._check(self.lib.bftkv_gpu_selftest_ecdsa_keyset_table(self.h, keyset, key, words.ctypes.data, len(words)), "selftest_ecdsa_keyset_table")
+        return words
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -720,6 +790,15 @@ class Batcher:
         dg, sg, kk = _u8(digest), _u8(sig), _u8(key)
         valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
         rc = self.lib.bftkv_gpu_batcher_ecdsa_verify(self.h, _ptr(dg), len(digest), _ptr(sg), _ptr(kk), _ptr(cb), bits, _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
+
+    def ecdsa_verify_keyset(self, keyset: int, key: int, digest: bytes, sig: bytes):
+        """crypto/ecdsa.Verify for one raw signature r || s under key `key` of a resident key set -> (rc, status, valid)."""
+        if not digest or len(sig) != 2 * self.ctx._ecdsa_keyset_fbytes(keyset):
+            raise ValueError("ecdsa_verify_keyset: sig of 2 fbytes of the set's curve, a non-empty digest")
+        dg, sg = _u8(digest), _u8(sig)
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_ecdsa_verify_keyset(self.h, keyset, key, _ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
         return rc, int(st[0]), int(valid[0])
 
     def modexp(self, base: int, exp: int, mod: int, nbytes: int = 256, exp_len: int = 32):

@@ -278,7 +278,8 @@ struct bftkv_gpu_batcher {
     int kind;                  // 0 collective verify, 1 signature verify, 2 transport message (tbs = the packet sequence),
                                // 3 Issuer + VerifyWithCertificate over a request certificate (cert / cert_len below),
                                // 4..7 ONE threshold share-combine operation (th_* below): 4 prod psig mod N, 5 sum l_j y_j mod m,
-                               // 6 CalculateR, 7 b^x mod n, 8 ECDSA CalculateR
+                               // 6 CalculateR, 7 b^x mod n, 8 ECDSA CalculateR, 9 ECDSA verification (key in the call),
+                               // 10 ECDSA verification under a resident key set (quorum = the set's handle)
     int quorum;
     const uint8_t* tbs; uint64_t tbs_len;
     const uint8_t* sig; uint64_t sig_len;
@@ -301,13 +302,14 @@ struct bftkv_gpu_batcher {
     uint8_t* fname_out = nullptr; uint8_t fname_len = 0;
     // kinds 0 / 1: SHA-256 state after the whole blocks of tbs, absorbed by the caller's own thread in submit()
     uint32_t mid[8] = {};
-    // kinds 4..9: one operation of th_k terms over numbers of th_nbytes (th_qbytes: the order's width for CalculateR, the exponent's
+    // kinds 4..10: one operation of th_k terms over numbers of th_nbytes (th_qbytes: the order's width for CalculateR, the exponent's
     // for kind 7); requests of one SHAPE (kind, k, widths) share a device call, whatever their moduli
     uint64_t th_shape = 0;
     uint32_t th_k = 0, th_nbytes = 0, th_qbytes = 0;
     const int32_t* th_xs = nullptr;
     const uint8_t *th_a = nullptr, *th_b = nullptr, *th_mod = nullptr, *th_mod2 = nullptr;
     uint8_t* th_out = nullptr;
+    uint32_t ks_key = 0;       // kind 10: the key's index within the set
   };
   struct Batch {
     std::vector<Req*> reqs;
@@ -509,11 +511,50 @@ struct bftkv_gpu_batcher {
     }
   }
 
+  // kind 10: ECDSA verification under a resident key set.  A group's callers share the set (Req::quorum: the lane is a fork and
+  // passes the handle through) and a digest length (th_k); th_a = digest, th_b = r || s, ks_key = the key's index in the set.  The
+  // lane holds its hold on the root's tables from the look at the set's curve to the end of the call, so the set cannot be
+  // replaced by one of another signature length in between.  2 f bytes of every caller's signature are copied with f taken from the
+  // set found NOW: a caller that retired the set while this request waited, and let a set of a wider curve take the handle, has
+  // broken the rule in include/bftkv_gpu.h (no destroy while calls naming the set are in flight) and the copy reads past its buffer.
+  void run_ecdsa_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k;
+    std::vector<uint8_t> valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    int rc;
+    {
+      ctx_lock lk(lane.ctx->mu);
+      KtRead kr(lane.ctx);
+      const EcKeySet* ks = kr.rc ? nullptr : ec_keyset_find(lane.ctx, r0.quorum);
+      if (kr.rc) rc = kr.rc;
+      else if (!ks) rc = BFTKV_E_INVALID;
+      else {
+        const uint32_t f = (ks->bits + 7) / 8;
+        std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * f);
+        std::vector<uint32_t> idx(n);
+        for (uint32_t i = 0; i < n; ++i) {
+          memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
+          memcpy(&sg[(size_t)i * 2 * f], g[i]->th_b, 2 * (size_t)f);
+          idx[i] = g[i]->ks_key;
+        }
+        rc = ecdsa_verify_keyset_impl(lane.ctx, r0.quorum, n, dg.data(), dlen, sg.data(), idx.data(), valid.data(), st.data(), false);
+        ++device_calls;
+      }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(10) : st[i];
+      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
+    }
+  }
+
   void run_threshold(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const int kind = r0.kind;
     if (kind == 8) { run_ecdsa(lane, g, device_calls); return; }
     if (kind == 9) { run_ecdsa_verify(lane, g, device_calls); return; }
+    if (kind == 10) { run_ecdsa_verify_keyset(lane, g, device_calls); return; }
     const uint32_t n = (uint32_t)g.size(), k = r0.th_k, nb = r0.th_nbytes, qb = r0.th_qbytes;
     // (CalculateR: a group (p, q) is one table row)
     std::map<std::string, uint32_t> slot;
@@ -869,6 +910,20 @@ int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, 
   r.th_shape = (uint64_t)9 | (uint64_t)dlen << 8 | (uint64_t)bit_size << 24;
   r.th_k = dlen; r.th_nbytes = (bit_size + 7) / 8; r.th_qbytes = bit_size; r.th_a = digest; r.th_b = sig; r.th_mod = curve; r.th_mod2 = key;
   r.th_out = valid_out;
+  const int rc = b->submit(r);
+  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
+  if (rc) *valid_out = 0;
+  return rc;
+}
+
+int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen, const uint8_t* sig,
+                                          uint8_t* valid_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (valid_out) *valid_out = 0;
+  if (!b || !status_out || !valid_out || !digest || !sig || dlen == 0 || dlen > 66) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r{10, keyset, nullptr, 0, nullptr, 0, false, 0};       // (an unknown handle fails its own group alone)
+  r.th_shape = (uint64_t)10 | (uint64_t)dlen << 8;
+  r.th_k = dlen; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
   const int rc = b->submit(r);
   *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
   if (rc) *valid_out = 0;

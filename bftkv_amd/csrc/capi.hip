@@ -91,6 +91,20 @@ struct QuorumHost {
   uint32_t ids_off[MAX_QC + 1];
 };
 
+// A resident ECDSA key set (ec_capi.inc): one fixed-base table per key, built on the device at registration
+struct EcKeySet {
+  bool live = false;
+  int curve_id = -1;                       // index into kEcCurves
+  uint32_t bits = 0, n_keys = 0, n_refused = 0;
+  uint32_t w = 0, nwin = 0;                // window bits (the width of the context's G table when the set was made) and windows
+  size_t key_words = 0;                    // fb_table_words of one key
+  std::vector<uint8_t> curve;              // P || N || B || Gx || Gy
+  DevBuf tab;                              // [n_keys][key_words]; the rows of a refused key are zero
+  DevBuf refused;                          // [n_keys] bytes: 1 = elliptic.Unmarshal refuses the key
+  DevBuf mod[4];                           // N as a ModTab for k_modinv (the set's own copy: no call uploads anything)
+  void release() { tab.release(); refused.release(); for (DevBuf& b : mod) b.release(); }
+};
+
 }  // namespace
 
 using ctx_lock = std::lock_guard<std::recursive_mutex>;
@@ -145,6 +159,7 @@ struct bftkv_gpu_ctx {
   KeyTableDev kt{};
 
   std::vector<QuorumHost> quorums;
+  std::vector<EcKeySet> ec_keysets;    // root: the handles of bftkv_gpu_ecdsa_keyset_create; forks read them under KtRead, without a copy
 
   // per-call arena
   DevBuf txt_mid32, txt_mid64, txt_tail, txt_len;     // text-mode hashing state (TextDev)
@@ -234,7 +249,7 @@ namespace {
 
 int fork_refresh(bftkv_gpu_ctx* c);
 
-// Exclusive access to the key table / quorum descriptors of a root context (see bftkv_gpu_ctx::root).
+// Exclusive access to the key table / quorum descriptors / ECDSA key sets of a root context (see bftkv_gpu_ctx::root).
 struct KtWrite {
   bftkv_gpu_ctx* c;
   explicit KtWrite(bftkv_gpu_ctx* c_) : c(c_) { c->kt_writers.fetch_add(1); c->kt_rw.lock(); }
@@ -1234,6 +1249,7 @@ void bftkv_gpu_destroy(bftkv_gpu_ctx* c) {
                     &c->in_ss, &c->in_ss_off, &c->in_prefix, &c->in_prefix_off, &c->in_shared, &c->in_shared_off, &c->in_seg, &c->st_tmp, &c->item_tmp, &c->bits_tmp, &c->plan_cut, &c->txt_mid32, &c->txt_mid64, &c->txt_tail, &c->txt_len})
     b->release();
   for (auto& q : c->quorums) { q.member.release(); q.ids.release(); }
+  for (EcKeySet& ks : c->ec_keysets) ks.release();
   c->in_pack.release();
   c->forced_iss.release();
   release_small_pin(c);

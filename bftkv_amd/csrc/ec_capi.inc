@@ -1,6 +1,6 @@
 // C ABI of the threshold-ECDSA entry points (include/bftkv_gpu.h): CalculateR and CalculatePartialR of
-// crypto/threshold/ecdsa/ecdsa.go over crypto/elliptic's four curves, and crypto/ecdsa.Verify on raw signatures.  Kernels:
-// ec_kernels.hip.
+// crypto/threshold/ecdsa/ecdsa.go over crypto/elliptic's four curves, and crypto/ecdsa.Verify on raw signatures, with the key
+// in the call or in a resident key set.  Kernels: ec_kernels.hip.
 namespace {
 
 // The groups the library recognises, by value: P, N, B, Gx, Gy (big-endian hex) and BitSize of crypto/elliptic's curves.  The
@@ -252,6 +252,206 @@ int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, 
   return finish(c, dev);
 }
 
+// ---- resident key sets ----------------------------------------------------------------------------------------------------
+// A long-lived key (the distributed CA key of a threshold signature) is registered once: elliptic.Unmarshal's checks and a
+// fixed-base table per key run on the device at bftkv_gpu_ecdsa_keyset_create, and every verification after that takes u2 Q
+// from the key's table as it takes u1 G from the curve's.  Sets live on the root context like quorums: created and destroyed
+// there under KtWrite (the forks' calls in flight drain first), read by the forks under KtRead without a copy.
+constexpr uint32_t EC_KEYSET_MAX_KEYS = 4096;
+constexpr size_t EC_KEYSET_TMP_BYTES = (size_t)256 << 20;      // k_ec_keytab_build's temporaries per launch: the keys go in chunks
+
+// caller holds c->mu and, on a fork, the root's key-table lock (KtRead)
+const EcKeySet* ec_keyset_find(const bftkv_gpu_ctx* c, int keyset) {
+  const bftkv_gpu_ctx* r = c->root ? c->root : c;
+  if (keyset < 0 || (size_t)keyset >= r->ec_keysets.size() || !r->ec_keysets[keyset].live) return nullptr;
+  return &r->ec_keysets[keyset];
+}
+
+int ecdsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, int* keyset_out) {
+  if (!c || !keys || !curve || !keyset_out || bit_size == 0 || bit_size > 521 || n_keys == 0 || n_keys > EC_KEYSET_MAX_KEYS) return BFTKV_E_INVALID;
+  const int id = ec_curve_id(curve, bit_size);
+  if (id < 0) return BFTKV_E_UNSUPPORTED;
+  const uint32_t f = (bit_size + 7) / 8;
+  ctx_lock lk(c->mu);
+  if (c->root) return fail(c, BFTKV_E_STATE, "ECDSA key sets are created on the root context; its forks see them");
+  HIPCHK(c, hipSetDevice(c->device));
+  ScratchBufs sb(c);
+  { int grc = modtab_gc(c); if (grc) return grc; }
+  EcKeySet ks;
+  DevBuf tmp;
+  int rc = 0;
+  auto build = [&]() -> int {
+    ks.curve_id = id; ks.bits = bit_size; ks.n_keys = n_keys;
+    ks.curve.assign(curve, curve + 5 * (size_t)f);
+    // N's Montgomery rows for k_modinv, copied out of the context's cache (which may drop them) into the set
+    ModTab mq;
+    if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq))) return rc;
+    const void* src[4] = {mq.n_limbs, mq.r2_limbs, mq.n0inv, mq.r2w_limbs};
+    const size_t len[4] = {MONT_N * 4, MONT_N * 4, 4, MONT_N_WIDE * 4};
+    for (int k = 0; k < 4; ++k) {
+      if (ks.mod[k].ensure(len[k]) != hipSuccess) { (void)hipGetLastError(); return fail(c, BFTKV_E_NOMEM, "ECDSA key set: device allocation failed"); }
+      HIPCHK(c, hipMemcpyAsync(ks.mod[k].p, src[k], len[k], hipMemcpyDeviceToDevice, c->stream));
+    }
+    uint8_t* d_keys;
+    if ((rc = to_dev(c, sb, keys, (size_t)n_keys * (1 + 2 * f), &d_keys))) return rc;
+    ec_dispatch(id, curve, [&](auto C) {
+      constexpr int L = decltype(C)::kWords;
+      const uint32_t* gtab;
+      if ((rc = ec_fb_table<L>(c, id, C, &gtab, &ks.w, &ks.nwin))) return;          // the set keeps the width of the G table for life
+      ks.key_words = ecf::fb_table_words<L>(ks.w, ks.nwin);
+      const size_t tab_bytes = (size_t)n_keys * ks.key_words * 4, per = ((size_t)1 << ks.w) - 1;
+      const size_t key_tmp = (size_t)ks.nwin * per * 2 * L * 4;
+      const uint32_t chunk = (uint32_t)std::min<size_t>(n_keys, std::max<size_t>(1, EC_KEYSET_TMP_BYTES / key_tmp));
+      if (ks.tab.ensure_exact(tab_bytes) != hipSuccess || ks.refused.ensure(n_keys) != hipSuccess || tmp.ensure_exact(chunk * key_tmp) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(c, BFTKV_E_NOMEM, "ECDSA key set: device allocation failed");
+        return;
+      }
+      if (hipMemsetAsync(ks.tab.p, 0, tab_bytes, c->stream) != hipSuccess) { rc = fail(c, BFTKV_E_DEVICE, "hipMemsetAsync"); return; }
+      for (uint32_t k0 = 0; k0 < n_keys; k0 += chunk) {
+        const uint32_t nk = std::min(chunk, n_keys - k0);
+        hipLaunchKernelGGL(k_ec_keytab_build<L>, dim3((nk * ks.nwin + EC_BLOCK - 1) / EC_BLOCK), dim3(EC_BLOCK), 0, c->stream, nk,
+                           (const uint8_t*)d_keys + (size_t)k0 * (1 + 2 * f), C, ks.w, ks.nwin, tmp.as<uint32_t>(),
+                           ks.tab.as<uint32_t>() + (size_t)k0 * ks.key_words, ks.refused.as<uint8_t>() + k0);
+      }
+    });
+    if (rc) return rc;
+    std::vector<uint8_t> refused(n_keys);
+    HIPCHK(c, hipMemcpyAsync(refused.data(), ks.refused.p, n_keys, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    for (uint8_t r : refused) ks.n_refused += r != 0;
+    return 0;
+  };
+  rc = build();
+  tmp.release();
+  if (rc) { ks.release(); return rc; }
+  ks.live = true;
+  int h = -1;
+  for (size_t i = 0; i < c->ec_keysets.size(); ++i) if (!c->ec_keysets[i].live) { h = (int)i; break; }
+  KtWrite kw(c);
+  if (h < 0) { c->ec_keysets.emplace_back(); h = (int)c->ec_keysets.size() - 1; }
+  c->ec_keysets[h] = std::move(ks);
+  *keyset_out = h;
+  return 0;
+}
+
+int ecdsa_keyset_destroy_impl(bftkv_gpu_ctx* c, int keyset) {
+  if (!c) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  if (c->root) return fail(c, BFTKV_E_STATE, "ECDSA key sets are destroyed on the root context");
+  if (!ec_keyset_find(c, keyset)) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle");
+  HIPCHK(c, hipSetDevice(c->device));
+  KtWrite kw(c);
+  HIPCHK(c, hipDeviceSynchronize());          // (_dev calls return before their kernels have run: nothing may still read the tables)
+  c->ec_keysets[keyset].release();
+  c->ec_keysets[keyset] = EcKeySet();
+  return 0;
+}
+
+int ecdsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* window_bits_out,
+                           uint64_t* table_bytes_out) {
+  if (!c) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const EcKeySet* ks = ec_keyset_find(c, keyset);
+  if (!ks) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle");
+  if (n_keys_out) *n_keys_out = ks->n_keys;
+  if (n_refused_out) *n_refused_out = ks->n_refused;
+  if (window_bits_out) *window_bits_out = ks->w;
+  if (table_bytes_out) *table_bytes_out = (uint64_t)ks->n_keys * ks->key_words * 4;
+  return 0;
+}
+
+// one key's table, as built (test hook)
+int ecdsa_keyset_table_impl(bftkv_gpu_ctx* c, int keyset, uint32_t key, uint32_t* words_out, uint64_t cap_words) {
+  if (!c || !words_out) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const EcKeySet* ks = ec_keyset_find(c, keyset);
+  if (!ks || key >= ks->n_keys) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle or key index");
+  if (cap_words < ks->key_words) return fail(c, BFTKV_E_NOMEM, "words_out holds less than one table");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(words_out, ks->tab.as<uint32_t>() + (size_t)key * ks->key_words, ks->key_words * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ecdsa_verify_impl over a registered set: the same k_ecv_prep, k_modinv and k_ecv_base, then k_ecv_key_tab.  Nothing is read
+// from host memory but the host form's own arrays (N's rows and both tables are resident), so the device form never waits.
+int ecdsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                             const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out, bool dev) {
+  if (!c || n_ops > (1u << 24) || (n_ops && (!valid_out || !status_out))) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if (n_ops) {                                 // fail closed: whatever refuses the call below leaves failures behind
+    if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
+    if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
+    else memset(valid_out, 0, n_ops);
+  }
+  if (dlen == 0 || dlen > 66 || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const EcKeySet* ks = ec_keyset_find(c, keyset);
+  if (!ks) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle");
+  const uint32_t f = (ks->bits + 7) / 8;
+  if (n_ops == 0) return 0;
+  const bftkv_gpu_ctx* r = c->root ? c->root : c;
+  const int id = ks->curve_id;
+  // The root's G table is read here without the root's own lock (a fork holds KtRead, not r->mu).  That is safe because the root
+  // never rebuilds it: the window width is fixed when the context is made, ec_fb_table fills ec_fb_tab[id] / ec_fb_w[id] once per
+  // curve, and the set's creation did that before any fork could name the set.  So the check below cannot fail today; it is
+  // there for the day a context may change its width, which would have to take KtWrite.
+  if (r->ec_fb_w[id] != ks->w) return fail(c, BFTKV_E_STATE, "the G table of the key set's width is gone");
+  const uint32_t* gtab = r->ec_fb_tab[id].as<uint32_t>();
+  ScratchBufs sb(c);
+  ModTab mq;
+  mq.n_limbs = ks->mod[0].as<uint32_t>(); mq.r2_limbs = ks->mod[1].as<uint32_t>(); mq.n0inv = ks->mod[2].as<uint32_t>();
+  mq.r2w_limbs = ks->mod[3].as<uint32_t>();
+  uint32_t *d_gi, *d_ki = nullptr;
+  uint8_t *d_dg, *d_sig;
+  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2, *d_valid, *d_st;
+  if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
+  if (key_idx) {                                                                       // clamped on the device, for host callers too
+    uint32_t* raw;
+    if ((rc = to_dev(c, sb, key_idx, n_ops, &raw, dev)) || (rc = idx_to_dev(c, sb, raw, n_ops, ks->n_keys, &d_ki, true))) return rc;
+  }
+  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
+  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * f, &d_sig, dev))) return rc;
+  if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
+      (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
+    return rc;
+  if (dev) { d_valid = valid_out; d_st = status_out; }
+  else if ((rc = dev_alloc(c, sb, n_ops, &d_valid, false)) || (rc = dev_alloc(c, sb, n_ops, &d_st, false))) return rc;
+  hipStream_t s = c->stream;
+  ec_dispatch(id, ks->curve.data(), [&](auto C) {
+    constexpr int L = decltype(C)::kWords;
+    if ((rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_u2, false)) ||
+        (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_r, false)) ||
+        (rc = dev_alloc(c, sb, (size_t)n_ops * 3 * L * 4, &d_pt, false)))
+      return;
+    const dim3 grid((n_ops + EC_BLOCK - 1) / EC_BLOCK), block(EC_BLOCK);
+    hipLaunchKernelGGL(k_ecv_prep<L>, grid, block, 0, s, n_ops, (const uint8_t*)d_dg, dlen, ks->bits, (const uint8_t*)d_sig, C, (uint32_t*)d_s28,
+                       (uint32_t*)d_e, (uint32_t*)d_r, (uint8_t*)d_flag);
+    hipLaunchKernelGGL(k_modinv, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint32_t*)d_s28, (const uint32_t*)d_gi, mq, (uint32_t*)d_w28,
+                       (uint8_t*)d_ibad, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+    hipLaunchKernelGGL(k_ecv_base<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint32_t*)d_e, (const uint32_t*)d_w28,
+                       (const uint8_t*)d_flag, C, gtab, ks->w, ks->nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
+    hipLaunchKernelGGL(k_ecv_key_tab<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, ks->tab.as<uint32_t>(), ks->refused.as<uint8_t>(),
+                       (const uint32_t*)d_ki, ks->n_keys, ks->w, ks->nwin, (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag,
+                       (const uint8_t*)d_ibad, C, (uint8_t*)d_valid, (uint8_t*)d_st);
+  });
+  if (rc) return rc;
+  if (!dev) {
+    HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
+  }
+  return finish(c, dev);
+}
+
 }  // namespace
 
 extern "C" {
@@ -276,6 +476,26 @@ int bftkv_gpu_ecdsa_verify(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* dige
 int bftkv_gpu_ecdsa_verify_dev(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, const uint32_t* key_idx,
                                uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out) {
   return ecdsa_verify_impl(c, n_ops, digests, dlen, sigs, key_idx, n_keys, keys, curve, bit_size, valid_out, status_out, true);
+}
+
+int bftkv_gpu_ecdsa_keyset_create(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, int* keyset_out) {
+  return ecdsa_keyset_create_impl(c, n_keys, keys, curve, bit_size, keyset_out);
+}
+int bftkv_gpu_ecdsa_keyset_destroy(bftkv_gpu_ctx* c, int keyset) { return ecdsa_keyset_destroy_impl(c, keyset); }
+int bftkv_gpu_ecdsa_keyset_info(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* window_bits_out,
+                                uint64_t* table_bytes_out) {
+  return ecdsa_keyset_info_impl(c, keyset, n_keys_out, n_refused_out, window_bits_out, table_bytes_out);
+}
+int bftkv_gpu_ecdsa_verify_keyset(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                  const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out) {
+  return ecdsa_verify_keyset_impl(c, keyset, n_ops, digests, dlen, sigs, key_idx, valid_out, status_out, false);
+}
+int bftkv_gpu_ecdsa_verify_keyset_dev(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                      const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out) {
+  return ecdsa_verify_keyset_impl(c, keyset, n_ops, digests, dlen, sigs, key_idx, valid_out, status_out, true);
+}
+int bftkv_gpu_selftest_ecdsa_keyset_table(bftkv_gpu_ctx* c, int keyset, uint32_t key, uint32_t* words_out, uint64_t cap_words) {
+  return ecdsa_keyset_table_impl(c, keyset, key, words_out, cap_words);
 }
 
 }  // extern "C"

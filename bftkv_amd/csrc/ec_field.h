@@ -376,8 +376,9 @@ EC_HD bool x_matches_r(const Jac<L>& R, const uint32_t* r, const Curve<L>& C) {
   return fe_eq<L>(t, R.x);
 }
 
-// The fixed-base table of a curve: the affine points j 2^(w i) G in Montgomery form, windows i = 0 .. nwin - 1 of w bits (nwin w
-// covers the scalar), digits j = 1 .. 2^w - 1.  Word-major inside a window: word k (k < L: x, k >= L: y) of digit j is
+// The fixed-base table of a point B (the curve's G, or a registered key): the affine points j 2^(w i) B in Montgomery form, windows
+// i = 0 .. nwin - 1 of w bits (nwin w covers the scalar), digits j = 1 .. 2^w - 1.  Word-major inside a window: word k (k < L: x,
+// k >= L: y) of digit j is
 //   tab[((i 2L + k) << w) + j]       (slot j = 0 unused, zero)
 // so the 64 lanes of a wave, which walk the same window with their own digits, read one word of their entries from one 2^w-word
 // run (64 bytes at w = 4: one line per load instruction, whatever the digits).
@@ -385,7 +386,7 @@ EC_HD uint32_t fb_windows(uint32_t fbytes, uint32_t w) { return (8u * fbytes + w
 template <int L>
 EC_HD size_t fb_table_words(uint32_t w, uint32_t nwin) { return ((size_t)nwin * 2 * L) << w; }
 
-// k G for k < 2^(w nwin) (L words) from the table: one mixed addition per non-zero digit, no doubling.  The digits come off a
+// k B for k < 2^(w nwin) (L words) from the table of B: one mixed addition per non-zero digit, no doubling.  The digits come off a
 // copy of k that is shifted down, so that no register array is indexed by a variable.
 template <int L>
 EC_HD void fb_mul(Jac<L>& R, const uint32_t* tab, uint32_t w, uint32_t nwin, const uint32_t* k, const Curve<L>& C) {
@@ -444,18 +445,20 @@ EC_HD void curve_setup(Curve<L>& C, const uint8_t* be, uint32_t fbytes) {
   for (int i = 0; i < L; ++i) { const uint64_t v = (uint64_t)C.p[i] - br; C.pm2[i] = (uint32_t)v; br = v >> 63; }
 }
 
-// The fixed-base table of fb_mul (tab: fb_table_words<L>(w, nwin) words), host only.  Window i's points are sums of
-// B_i = 2^(w i) G through the exact pt_add; all of them are made affine with ONE field inversion (Montgomery's trick: no
-// j 2^(w i) is a multiple of the prime N > 2^w, so every Z is non-zero).
+// The fixed-base table of fb_mul (tab: fb_table_words<L>(w, nwin) words) for the base point (bx, by), affine in Montgomery form,
+// host only.  Window i's points are sums of B_i = 2^(w i) B through the exact pt_add; all of them are made affine with ONE field
+// inversion (Montgomery's trick: the curves have prime order N > 2^w and cofactor 1, so no j 2^(w i) B of a point B on the curve
+// is infinity and every Z is non-zero).  Every word written is fully reduced, so the table of a base is unique: the device build
+// of a key set (ec_kernels.hip k_ec_keytab_build) is checked against this one word for word.
 template <int L>
-inline void fb_table_build(uint32_t* tab, uint32_t w, uint32_t nwin, const Curve<L>& C) {
+inline void fb_table_build(uint32_t* tab, uint32_t w, uint32_t nwin, const uint32_t* bx, const uint32_t* by, const Curve<L>& C) {
   const uint32_t per = (1u << w) - 1u;
   const size_t n = (size_t)nwin * per;
   std::vector<Jac<L>> pts(n);
   std::vector<uint32_t> pre(n * L);
   Jac<L> base;
-  fe_copy<L>(base.x, C.gx);
-  fe_copy<L>(base.y, C.gy);
+  fe_copy<L>(base.x, bx);
+  fe_copy<L>(base.y, by);
   fe_copy<L>(base.z, C.one);
   for (uint32_t i = 0; i < nwin; ++i) {
     Jac<L>* row = &pts[(size_t)i * per];
@@ -480,6 +483,11 @@ inline void fb_table_build(uint32_t* tab, uint32_t w, uint32_t nwin, const Curve
     uint32_t* e = tab + (((size_t)(i / per) * 2 * L) << w) + (i % per + 1);
     for (int k = 0; k < L; ++k) { e[(size_t)k << w] = pts[i].x[k]; e[(size_t)(L + k) << w] = pts[i].y[k]; }
   }
+}
+// ... of the curve's own base point G
+template <int L>
+inline void fb_table_build(uint32_t* tab, uint32_t w, uint32_t nwin, const Curve<L>& C) {
+  fb_table_build<L>(tab, w, nwin, C.gx, C.gy, C);
 }
 
 }  // namespace ecf

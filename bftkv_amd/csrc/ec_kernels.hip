@@ -5,6 +5,7 @@
 //   k_ec_calc_r_op  thread / operation: both of the above in one lane (the split for calls with many terms per SIMD)
 //   k_ec_base_mult  thread / scalar: Marshal(s G)                                                             CalculatePartialR
 //   k_ecv_prep / k_ecv_base / k_ecv_key   thread / signature: ecdsa.Verify on raw r || s (further down)        Verify
+//   k_ec_keytab_build / k_ecv_key_tab     resident key sets: a table per key, u2 Q from it (at the end)         Verify
 // w = v^-1 mod N is folded into the per-term scalars: the curves have prime order, so sum (l_j w) R_j = w sum l_j R_j and
 // the scaled prefix sums meet +-T_j and infinity exactly where the reference's unscaled ones do.
 // Status bytes: bit 2 = fenced (the reference decides), bit 1 = v has no inverse (k_modinv's); copy_status normalises.
@@ -280,6 +281,102 @@ __global__ void __launch_bounds__(EC_BLOCK) k_ecv_key(uint32_t n_ops, const uint
 #pragma unroll
     for (int i = 0; i < L; ++i) x[i] = u2_in[(uint64_t)op * L + i];
     ecf::pt_mul<L>(A, Q, x, C);                              // u2 Q: finite (0 < u2 < N, prime order)
+    ec_load_jac<L>(Q, pt_in + (uint64_t)op * 3 * L);         // u1 G
+    const int code = ecf::pt_add<L>(A, Q, A, C);
+    if (code == ecf::EC_ADD_EQUAL) st = BFTKV_TH_FENCED;     // Add's doubling case on the generic path
+    else if (code == ecf::EC_ADD_GENERAL) {                  // (opposite: the sum is infinity, INVALID)
+#pragma unroll
+      for (int i = 0; i < L; ++i) x[i] = r_in[(uint64_t)op * L + i];
+      valid = ecf::x_matches_r<L>(A, x, C) ? 1 : 0;
+    }
+  }
+  valid_out[op] = valid;
+  status_out[op] = st;
+}
+
+// ---- resident key sets (bftkv_gpu_ecdsa_keyset_*): a fixed-base table per key, built once on the device ------------------------
+// k_ec_keytab_build, a lane per (key, window i): Unmarshal's checks on the key (a refused key sets its byte and leaves its rows
+// zero), B = 2^(w i) Q by w i doublings, the multiples j B (j = 1 .. 2^w - 1) by the exact pt_add, made affine with one inversion
+// per lane (Montgomery's trick over the row; no Z is zero, ec_field.h fb_table_build).  The Jacobian X, Y wait in the row's own
+// table slots, Z and the running products of Z in tmp ([2^w - 1][2 L][n_lanes] words: a wave's stores are contiguous).  The result
+// is the table of fb_table_build with base Q, word for word: the affine Montgomery words are fully reduced, hence unique.
+// The lanes of a wave double a different number of times; registration is off the hot path and the worst lane costs one ladder's
+// doublings.  tab arrives zeroed (slot 0 of every run and the rows of refused keys stay zero).
+template <int L>
+__global__ void __launch_bounds__(EC_BLOCK) k_ec_keytab_build(uint32_t n_keys, const uint8_t* __restrict__ keys /*[n_keys][1 + 2 f]*/, ecf::Curve<L> C,
+                                                              uint32_t w, uint32_t nwin, uint32_t* __restrict__ tmp,
+                                                              uint32_t* __restrict__ tab /*[n_keys][fb_table_words]*/, uint8_t* __restrict__ refused) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, n_lanes = n_keys * nwin;
+  if (t >= n_lanes) return;
+  const uint32_t key = t / nwin, i = t % nwin, f = C.fbytes, per = (1u << w) - 1u;
+  const uint8_t* kb = keys + (uint64_t)key * (1 + 2 * f);
+  uint32_t a[L], b[L];
+  ecf::Jac<L> B, P;
+  ecf::fe_from_be<L>(a, kb + 1, f);
+  ecf::fe_from_be<L>(b, kb + 1 + f, f);
+  const bool ok = kb[0] == 4 && ecf::pt_check<L>(B.x, B.y, a, b, C);
+  if (i == 0) refused[key] = ok ? 0 : 1;
+  if (!ok) return;
+  ecf::fe_copy<L>(B.z, C.one);
+  for (uint32_t d = 0; d < w * i; ++d) ecf::pt_dbl<L>(B, B, C);
+  uint32_t* row = tab + (uint64_t)key * ecf::fb_table_words<L>(w, nwin) + (((size_t)i * 2 * L) << w);
+  uint32_t* zs = tmp + t;                                    // word k of Z_j: zs[(j 2L + k) n_lanes], of Z_0 .. Z_j: k + L
+  P = B;
+  ecf::fe_copy<L>(a, B.z);                                   // a: Z_0 ... Z_j
+  for (uint32_t j = 0; j < per; ++j) {
+    if (j) { ecf::pt_add<L>(P, P, B, C); ecf::fp_mul<L>(a, a, P.z, C); }
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+      row[((size_t)k << w) + j + 1] = P.x[k];
+      row[((size_t)(L + k) << w) + j + 1] = P.y[k];
+      zs[((uint64_t)j * 2 * L + k) * n_lanes] = P.z[k];
+      zs[((uint64_t)j * 2 * L + L + k) * n_lanes] = a[k];
+    }
+  }
+  uint32_t inv[L], zi[L];
+  ecf::fp_inv<L>(inv, a, C);                                 // 1 / (Z_0 ... Z_(per-1))
+  for (uint32_t j = per; j-- > 0;) {
+    if (j) {
+#pragma unroll
+      for (int k = 0; k < L; ++k) { a[k] = zs[((uint64_t)(j - 1) * 2 * L + L + k) * n_lanes]; b[k] = zs[((uint64_t)j * 2 * L + k) * n_lanes]; }
+      ecf::fp_mul<L>(zi, inv, a, C);                         // 1 / Z_j
+      ecf::fp_mul<L>(inv, inv, b, C);
+    } else ecf::fe_copy<L>(zi, inv);
+#pragma unroll
+    for (int k = 0; k < L; ++k) { a[k] = row[((size_t)k << w) + j + 1]; b[k] = row[((size_t)(L + k) << w) + j + 1]; }
+    ecf::fp_sqr<L>(P.z, zi, C);                              // (P is free in this pass: 1 / Z_j^2, then 1 / Z_j^3)
+    ecf::fp_mul<L>(a, a, P.z, C);
+    ecf::fp_mul<L>(P.z, P.z, zi, C);
+    ecf::fp_mul<L>(b, b, P.z, C);
+#pragma unroll
+    for (int k = 0; k < L; ++k) { row[((size_t)k << w) + j + 1] = a[k]; row[((size_t)(L + k) << w) + j + 1] = b[k]; }
+  }
+}
+
+// k_ecv_key with the key's table in place of the ladder: stands behind the same k_ecv_prep, k_modinv and k_ecv_base.  A key
+// refused at registration fences every signature that names it, before any other rule; u2 Q comes from fb_mul over the key's
+// table (set_tab + key * fb_table_words), and the two multiples still meet in ONE pt_add whose case code is the fence.
+template <int L>
+__global__ void __launch_bounds__(EC_BLOCK) k_ecv_key_tab(uint32_t n_ops, const uint32_t* __restrict__ r_in, const uint32_t* __restrict__ set_tab,
+                                                          const uint8_t* __restrict__ refused /*[n_keys]*/, const uint32_t* __restrict__ key_idx,
+                                                          uint32_t n_keys, uint32_t w, uint32_t nwin, const uint32_t* __restrict__ u2_in,
+                                                          const uint32_t* __restrict__ pt_in, const uint8_t* __restrict__ flag,
+                                                          const uint8_t* __restrict__ inv_bad, ecf::Curve<L> C, uint8_t* __restrict__ valid_out,
+                                                          uint8_t* __restrict__ status_out) {
+  const uint32_t op = blockIdx.x * blockDim.x + threadIdx.x;
+  if (op >= n_ops) return;
+  const uint32_t key = key_idx ? min(key_idx[op], n_keys - 1u) : 0u;
+  uint8_t valid = 0, st = BFTKV_TH_OK;
+  const uint8_t fl = flag[op];
+  if (refused[key]) st = BFTKV_TH_FENCED;                    // no reference key object holds this point
+  else if (fl == ECV_FENCED) st = BFTKV_TH_FENCED;
+  else if (inv_bad[op]) st = BFTKV_TH_FAILED;
+  else if (fl == ECV_GO) {
+    uint32_t x[L];
+    ecf::Jac<L> Q, A;
+#pragma unroll
+    for (int i = 0; i < L; ++i) x[i] = u2_in[(uint64_t)op * L + i];
+    ecf::fb_mul<L>(A, set_tab + (uint64_t)key * ecf::fb_table_words<L>(w, nwin), w, nwin, x, C);      // u2 Q: finite (0 < u2 < N)
     ec_load_jac<L>(Q, pt_in + (uint64_t)op * 3 * L);         // u1 G
     const int code = ecf::pt_add<L>(A, Q, A, C);
     if (code == ecf::EC_ADD_EQUAL) st = BFTKV_TH_FENCED;     // Add's doubling case on the generic path

@@ -392,6 +392,14 @@ int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const 
  * one else's verdict. */
 int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, const uint8_t* key,
                                    const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out);
+/* The same for ONE signature under key `key` of a resident key set (bftkv_gpu_ecdsa_keyset_create on the batcher's context):
+ * digest [dlen], sig [2 fbytes of the set's curve]; an index past the set is clamped to its last key.  Callers are grouped by key
+ * set and digest length.  An unknown or destroyed handle returns BFTKV_E_INVALID; whenever the return code is not 0, *status_out
+ * is BFTKV_TH_FAILED and *valid_out 0.  The lane reads 2 fbytes of `sig` for the curve the handle names when the request RUNS, not
+ * when it was made: the caller must not destroy a set (whose handle a later set, perhaps of a wider curve, may take) while calls
+ * that name it are in flight. */
+int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen,
+                                          const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -570,6 +578,37 @@ int bftkv_gpu_ecdsa_verify(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* di
 int bftkv_gpu_ecdsa_verify_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
                                const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size,
                                uint8_t* valid_out, uint8_t* status_out);
+
+/* Resident key sets: the keys of bftkv_gpu_ecdsa_verify registered once, for callers whose keys outlive a call (the distributed CA
+ * key of a threshold signature).  keys [n_keys][1 + 2 fbytes] elliptic.Marshal bytes, 1 <= n_keys <= 4096; curve, bit_size and
+ * BFTKV_E_UNSUPPORTED as for bftkv_gpu_ecdsa_calculate_r.  elliptic.Unmarshal's checks run once, on the device, and every key that
+ * passes gets a fixed-base table there (affine j 2^(w i) Q, the layout of the curve's G table; w = the width of the context's G
+ * table, 4 bits, kept for the set's life): 49 KB per key on P-224, 64 KB on P-256, 144 KB on P-384, 281 KB on P-521.  A key that
+ * Unmarshal refuses does not refuse the set (the call still returns 0): it gets no table, is counted in n_refused_out, and every
+ * signature that names it is BFTKV_TH_FENCED.  Like quorums, sets are created and destroyed on the root context (a fork:
+ * BFTKV_E_STATE; the root waits for its forks' calls in flight) and read by its forks and batcher lanes; bftkv_gpu_destroy
+ * releases what is left.  A failed device allocation is BFTKV_E_NOMEM; an unknown or destroyed handle BFTKV_E_INVALID.
+ * A destroyed handle is handed out again by a later create, so retire a set only when no call that names it is in flight (batcher
+ * calls included: they size the signature by the set they find when they run). */
+int bftkv_gpu_ecdsa_keyset_create(bftkv_gpu_ctx* ctx, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size,
+                                  int* keyset_out);
+int bftkv_gpu_ecdsa_keyset_destroy(bftkv_gpu_ctx* ctx, int keyset);
+/* any of the outputs may be NULL; table_bytes_out = n_keys tables (refused keys hold zeroed ones) */
+int bftkv_gpu_ecdsa_keyset_info(bftkv_gpu_ctx* ctx, int keyset, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* window_bits_out,
+                                uint64_t* table_bytes_out);
+/* bftkv_gpu_ecdsa_verify under the keys of a set: for every input the same (valid, status) as that entry gives for the same digest,
+ * signature and key bytes, with u2 Q taken from the key's table instead of a ladder.  key_idx [n_ops] indexes the set (NULL: key 0,
+ * an index past the set is clamped to its last key); sigs are [n_ops][2 fbytes] of the set's curve; 1 <= dlen <= 66.  Whenever the
+ * return code is not 0 (a bad handle included) every status is BFTKV_TH_FAILED and every verdict 0; n_ops = 0 returns 0. */
+int bftkv_gpu_ecdsa_verify_keyset(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                  const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+/* same with digests / sigs / key_idx / valid_out / status_out resident in HBM: nothing is read from host memory, so the call is
+ * asynchronous on the context's stream and never waits for it. */
+int bftkv_gpu_ecdsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen,
+                                      const uint8_t* sigs, const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+/* Diagnostic: the table of key `key` of a set as the device built it, fb_table_words (windows x 2 L x 2^w) 32-bit words; all zero
+ * for a refused key.  BFTKV_E_NOMEM when cap_words is less than that.  The tests compare it with the host-built table. */
+int bftkv_gpu_selftest_ecdsa_keyset_table(bftkv_gpu_ctx* ctx, int keyset, uint32_t key, uint32_t* words_out, uint64_t cap_words);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

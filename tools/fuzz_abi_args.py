@@ -242,6 +242,63 @@ def ecdsa_verify_calls():
         note("batcher_ecdsa_verify", rc)
 
 
+def ecdsa_keyset_calls():
+    """The key-set entries: create (any key bytes: a refused key does not refuse the set), info, the test hook, verification through
+    the handle (host form, _dev form only where it is refused or has no operations, batcher) and destroy, with live, stale and
+    made-up handles.  Whatever comes back, a non-zero return leaves failures and no verdict."""
+    bits = rng.choice([0, 8, 224, 255, 256, 256, 384, 521, 522])
+    f = (bits + 7) // 8
+    n_keys = rng.choice([0, 1, 1, 2, 5, 4097])
+    cb = ec_curve(bits) if rng.random() < 0.95 else None
+    keys = buf(max(n_keys, 1) * (1 + 2 * f))
+    if rng.random() < 0.5:
+        keys[::1 + 2 * f] = 4
+    hs = C.c_int(-9)
+    rc = lib.bftkv_gpu_ecdsa_keyset_create(ctx, n_keys, p8(keys), p8(cb) if cb is not None else None, bits, C.byref(hs))
+    assert (rc == 0) == (hs.value >= 0), ("ecdsa_keyset_create", rc, hs.value)
+    note("ecdsa_keyset_create", rc)
+    live = rc == 0
+    handle = hs.value if live and rng.random() < 0.8 else rng.choice([-1, 0, 1, 7, 2 ** 31 - 1])
+    nk, nr, wb, tb = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+    rc = lib.bftkv_gpu_ecdsa_keyset_info(ctx, handle, C.byref(nk), C.byref(nr), C.byref(wb), C.byref(tb))
+    assert rc != 0 or (1 <= nk.value <= 4096 and nr.value <= nk.value and tb.value), ("ecdsa_keyset_info", nk.value, nr.value, tb.value)
+    note("ecdsa_keyset_info", rc)
+    known = rc == 0
+    sf = f if live and handle == hs.value else 66                  # signatures sized for the widest curve when the handle is a guess
+    words = np.zeros(rng.choice([0, 8, 80000]), dtype=np.uint32)
+    note("selftest_ecdsa_keyset_table", lib.bftkv_gpu_selftest_ecdsa_keyset_table(ctx, handle, rng.choice([0, 1, 4096]), words.ctypes.data_as(vp), len(words)))
+    n_ops = rng.choice([0, 1, 2, 5, 64])
+    dlen = rng.choice([0, 1, 20, 32, 48, 64, 66, 67, 4096])
+    dg, sg = buf(n_ops * min(dlen, 4096)), buf(n_ops * 2 * sf)
+    ki = np.array([rng.choice([0, 1, n_keys, 2 ** 32 - 1]) for _ in range(max(n_ops, 1))], dtype=np.uint32)
+    kip = ki.ctypes.data_as(vp) if rng.random() < 0.5 else None
+    valid, st = buf(n_ops, "zero"), buf(n_ops, "zero")
+    which = rng.randrange(3)
+    if which == 0:
+        rc = lib.bftkv_gpu_ecdsa_verify_keyset(ctx, handle, n_ops, p8(dg), dlen, p8(sg), kip, p8(valid), p8(st))
+        assert rc == 0 or (not valid[:n_ops].any() and (st[:n_ops] == 0xFF).all()), ("ecdsa_verify_keyset", rc)      # fail closed
+        assert rc != 0 or known, ("ecdsa_verify_keyset", handle)
+        note("ecdsa_verify_keyset", rc)
+    elif which == 1:
+        if rng.random() < 0.5:
+            n_ops = 0
+        else:
+            dlen = rng.choice([0, 67, 4096])
+            valid, st = None, None                      # (refused before anything is written: the arrays would have to live in HBM)
+        note("ecdsa_verify_keyset_dev", lib.bftkv_gpu_ecdsa_verify_keyset_dev(ctx, handle, n_ops, p8(dg), dlen, p8(sg), kip,
+                                                                             p8(valid) if valid is not None else None, p8(st) if st is not None else None))
+    else:
+        v1, s1 = C.c_uint8(0x55), C.c_uint8(0x55)
+        rc = lib.bftkv_gpu_batcher_ecdsa_verify_keyset(batcher, handle, rng.choice([0, 1, 2 ** 32 - 1]), p8(buf(min(dlen, 4096))), dlen, p8(buf(2 * sf)),
+                                                       C.byref(v1), C.byref(s1))
+        assert rc == 0 or (s1.value == 0xFF and v1.value == 0), ("batcher_ecdsa_verify_keyset", rc, s1.value, v1.value)      # fail closed
+        note("batcher_ecdsa_verify_keyset", rc)
+    if live:
+        rc = lib.bftkv_gpu_ecdsa_keyset_destroy(ctx, hs.value)
+        assert rc == 0, ("ecdsa_keyset_destroy", rc)
+    note("ecdsa_keyset_destroy", lib.bftkv_gpu_ecdsa_keyset_destroy(ctx, rng.choice([-1, hs.value, 3, 2 ** 31 - 1])))
+
+
 def offsets(n, total):
     o = np.zeros(n + 1, dtype=np.uint64)
     style = rng.random()
@@ -397,7 +454,7 @@ t0 = time.time()
 n = 0
 while time.time() - t0 < budget:
     rng.choice([threshold_batched, threshold_batched, threshold_one, verify_calls, verify_calls, keyring_and_quorum, cert_calls, cert_calls,
-                ecdsa_calls, ecdsa_verify_calls])()
+                ecdsa_calls, ecdsa_verify_calls, ecdsa_keyset_calls])()
     n += 1
 lib.bftkv_gpu_batcher_destroy(batcher)
 lib.bftkv_gpu_destroy(ctx)

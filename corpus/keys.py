@@ -94,11 +94,13 @@ def gen_prime(bits: int, rng: DRBG) -> int:
                     return n
 
 
-def gen_rsa(index: int, bits: int = 2048, seed: int = MASTER_SEED) -> Dict[str, int]:
+def gen_rsa(index: int, bits: int = 2048, seed: int = MASTER_SEED, e: int = 65537) -> Dict[str, int]:
+    """``bits`` may be any length, odd ones included: p takes the larger half.  gen_prime sets the top two bits of both primes, so
+    the product has exactly ``bits`` bits; for an even ``bits`` the stream of draws is what it always was (the caches stay valid).
+    ``e``: the public exponent; p, q are drawn again while phi is a multiple of it."""
     rng = DRBG("rsa", seed, bits, index)
-    e = 65537
     while True:
-        p = gen_prime(bits // 2, rng)
+        p = gen_prime(bits - bits // 2, rng)
         q = gen_prime(bits // 2, rng)
         if p == q:
             continue
@@ -141,7 +143,8 @@ def _cache_path(kind: str) -> str:
 
 
 def load_keys(kind: str, count: int) -> List[Dict[str, int]]:
-    """kind: 'rsa2048', 'rsa3072', 'rsa4096', 'dsa2048' (q 256 bits), or the other DSA sizes in use -- 'dsa1024' (q 160 bits: the
+    """kind: 'rsa<bits>' for a modulus of any bit length ('rsa<bits>e<exponent>' for a public exponent other than 65537: same draws, p and q
+    drawn again while phi is a multiple of it), 'dsa2048' (q 256 bits), or the other DSA sizes in use -- 'dsa1024' (q 160 bits: the
     group size of the reference's era and of its threshold tests, crypto/threshold/dsa/dsa_test.go:26-28), 'dsa1536' (q 224 bits,
     what gpg 2.2 makes of a 1536-bit request) and 'dsa3072' (q 256 bits).  Returns the first ``count`` keys, generating and
     extending the on-disk cache when it is short."""
@@ -152,7 +155,8 @@ def load_keys(kind: str, count: int) -> List[Dict[str, int]]:
             keys = json.load(f)["keys"]
     if len(keys) < count:
         if kind.startswith("rsa"):
-            gen = lambda i: gen_rsa(i, bits=int(kind[3:]))                     # noqa: E731
+            bits, _, e = kind[3:].partition("e")
+            gen = lambda i: gen_rsa(i, bits=int(bits), e=int(e or 65537))      # noqa: E731
         else:
             L = int(kind[3:])
             gen = lambda i: gen_dsa(i, L=L, N=DSA_Q_BITS[L])                   # noqa: E731

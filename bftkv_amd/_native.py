@@ -49,6 +49,7 @@ EXPORTS = [
     "bftkv_gpu_batcher_cert_entity", "bftkv_gpu_set_lagrange_x_bound", "bftkv_gpu_batcher_modmul_product", "bftkv_gpu_batcher_lagrange_combine", "bftkv_gpu_batcher_dsa_calculate_r", "bftkv_gpu_batcher_modexp",
     "bftkv_gpu_ecdsa_calculate_r", "bftkv_gpu_ecdsa_calculate_r_dev", "bftkv_gpu_batcher_ecdsa_calculate_r", "bftkv_gpu_ec_scalar_base_mult",
     "bftkv_gpu_ecdsa_verify", "bftkv_gpu_ecdsa_verify_dev", "bftkv_gpu_batcher_ecdsa_verify",
+    "bftkv_gpu_dsa_verify", "bftkv_gpu_dsa_verify_dev", "bftkv_gpu_batcher_dsa_verify",
     "bftkv_gpu_ecdsa_keyset_create", "bftkv_gpu_ecdsa_keyset_destroy", "bftkv_gpu_ecdsa_keyset_info", "bftkv_gpu_ecdsa_verify_keyset",
     "bftkv_gpu_ecdsa_verify_keyset_dev", "bftkv_gpu_batcher_ecdsa_verify_keyset", "bftkv_gpu_selftest_ecdsa_keyset_table",
 ]
@@ -144,6 +145,9 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_ecdsa_verify.argtypes = [vp, u32, u8p, u32, u8p, vp, u32, u8p, u8p, u32, u8p, u8p]
     lib.bftkv_gpu_ecdsa_verify_dev.argtypes = lib.bftkv_gpu_ecdsa_verify.argtypes
     lib.bftkv_gpu_batcher_ecdsa_verify.argtypes = [vp, u8p, u32, u8p, u8p, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_dsa_verify.argtypes = [vp, u32, u8p, u32, u8p, u32, vp, u32, u8p, vp, u32, u32, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_dsa_verify_dev.argtypes = lib.bftkv_gpu_dsa_verify.argtypes
+    lib.bftkv_gpu_batcher_dsa_verify.argtypes = [vp, u8p, u32, u8p, u32, u8p, u32, u8p, u8p, u8p, u8p, u8p]
     lib.bftkv_gpu_ecdsa_keyset_create.argtypes = [vp, u32, u8p, u8p, u32, C.POINTER(C.c_int)]
     lib.bftkv_gpu_ecdsa_keyset_destroy.argtypes = [vp, C.c_int]
     lib.bftkv_gpu_ecdsa_keyset_info.argtypes = [vp, C.c_int, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_uint64)]
@@ -605,6 +609,28 @@ class Context:
                                                     _ptr(cb), bits, _ptr(valid), _ptr(st)), "ecdsa_verify")
         return valid[:n], st[:n]
 
+    def dsa_verify(self, digests, sigs, keys, groups, key_idx=None, pbytes=None, qbytes=None):
+        """crypto/dsa.Verify on raw signatures: digests [n_ops] bytes of ONE length (1..64), sigs [n_ops] bytes r || s (2 qbytes each),
+        groups [(p, q, g)] ints, keys [(group, y)], key_idx [n_ops] or None (key 0) -> (valid, status), uint8 each.  pbytes / qbytes
+        default to the width of the widest p, g, y and to half a signature."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        if qbytes is None:
+            qbytes = len(sigs[0]) // 2 if n else max((int(g[1]).bit_length() + 7) // 8 for g in groups)
+        if pbytes is None:
+            pbytes = max(1, max((int(v).bit_length() + 7) // 8 for v in [g[0] for g in groups] + [g[2] for g in groups] + [k[1] for k in keys]))
+        if any(len(d) != dlen for d in digests) or any(len(s) != 2 * qbytes for s in sigs) or len(sigs) != n:
+            raise ValueError("dsa_verify: digests of one length, sigs of 2 qbytes")
+        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
+        p, q, g = (_ints_to_be([grp[i] for grp in groups], w) for i, w in ((0, pbytes), (1, qbytes), (2, pbytes)))
+        y = _ints_to_be([k[1] for k in keys], pbytes)
+        kg = np.ascontiguousarray([k[0] for k in keys], dtype=np.uint32)
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_dsa_verify(self.h, n, _ptr(dg), dlen, _ptr(sg), qbytes, None if ki is None else _ptr(ki), len(keys), _ptr(y),
+                                                  _ptr(kg), pbytes, len(groups), _ptr(p), _ptr(q), _ptr(g), _ptr(valid), _ptr(st)), "dsa_verify")
+        return valid[:n], st[:n]
+
     def ecdsa_keyset_create(self, keys, curve) -> int:
         """Register keys [n_keys] Marshal bytes (1 + 2 fbytes each) once: Unmarshal's checks and a table per key on the device.
         A refused key does not refuse the set (ecdsa_keyset_info counts it; its signatures are fenced)."""
@@ -790,6 +816,21 @@ class Batcher:
         dg, sg, kk = _u8(digest), _u8(sig), _u8(key)
         valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
         rc = self.lib.bftkv_gpu_batcher_ecdsa_verify(self.h, _ptr(dg), len(digest), _ptr(sg), _ptr(kk), _ptr(cb), bits, _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
+
+    def dsa_verify(self, digest: bytes, sig: bytes, group, y: int, pbytes=None):
+        """crypto/dsa.Verify for one raw signature r || s (2 qbytes) under group (p, q, g) and public value y -> (rc, status, valid)."""
+        qbytes = len(sig) // 2
+        if pbytes is None:
+            pbytes = max(1, max((int(v).bit_length() + 7) // 8 for v in (group[0], group[2], y)))
+        if not digest or not sig or len(sig) != 2 * qbytes:
+            raise ValueError("dsa_verify: sig of 2 qbytes, a non-empty digest")
+        dg, sg = _u8(digest), _u8(sig)
+        p, g, yy = (_ints_to_be([v], pbytes) for v in (group[0], group[2], y))
+        q = _ints_to_be([group[1]], qbytes)
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_dsa_verify(self.h, _ptr(dg), len(digest), _ptr(sg), qbytes, _ptr(yy), pbytes, _ptr(p), _ptr(q), _ptr(g),
+                                                   _ptr(valid), _ptr(st))
         return rc, int(st[0]), int(valid[0])
 
     def ecdsa_verify_keyset(self, keyset: int, key: int, digest: bytes, sig: bytes):

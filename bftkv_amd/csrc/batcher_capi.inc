@@ -279,7 +279,8 @@ struct bftkv_gpu_batcher {
                                // 3 Issuer + VerifyWithCertificate over a request certificate (cert / cert_len below),
                                // 4..7 ONE threshold share-combine operation (th_* below): 4 prod psig mod N, 5 sum l_j y_j mod m,
                                // 6 CalculateR, 7 b^x mod n, 8 ECDSA CalculateR, 9 ECDSA verification (key in the call),
-                               // 10 ECDSA verification under a resident key set (quorum = the set's handle)
+                               // 10 ECDSA verification under a resident key set (quorum = the set's handle), 11 DSA verification
+                               // (group and key in the call)
     int quorum;
     const uint8_t* tbs; uint64_t tbs_len;
     const uint8_t* sig; uint64_t sig_len;
@@ -310,6 +311,7 @@ struct bftkv_gpu_batcher {
     const uint8_t *th_a = nullptr, *th_b = nullptr, *th_mod = nullptr, *th_mod2 = nullptr;
     uint8_t* th_out = nullptr;
     uint32_t ks_key = 0;       // kind 10: the key's index within the set
+    const uint8_t *th_g = nullptr, *th_y = nullptr;      // kind 11: the group's generator and the public value (th_nbytes each)
   };
   struct Batch {
     std::vector<Req*> reqs;
@@ -549,9 +551,57 @@ struct bftkv_gpu_batcher {
     }
   }
 
+  // kind 11: DSA verification.  A group's callers share the widths and the digest length (th_k = dlen, th_nbytes = pbytes,
+  // th_qbytes = qbytes), whatever their groups and keys; th_a = digest, th_b = r || s, th_mod = p, th_mod2 = q, th_out = the verdict
+  // byte.  The distinct (p, q, g) of the batch make the call's group table in byte order (the same groups find their Montgomery
+  // rows in the context's cache call after call), the distinct (group, y) its key table.
+  void run_dsa_verify(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k, pb = r0.th_nbytes, qb = r0.th_qbytes;
+    auto group_key = [&](const Req* r) {
+      std::string k((const char*)r->th_mod, pb);
+      k.append((const char*)r->th_mod2, qb);
+      k.append((const char*)r->th_g, pb);
+      return k;
+    };
+    std::map<std::string, uint32_t> gslot, kslot;
+    for (Req* r : g) gslot.emplace(group_key(r), 0u);
+    uint32_t n_groups = 0;
+    std::vector<uint8_t> ps((size_t)gslot.size() * pb), qs((size_t)gslot.size() * qb), gs((size_t)gslot.size() * pb), ys;
+    for (auto& kv : gslot) {
+      kv.second = n_groups;
+      memcpy(&ps[(size_t)n_groups * pb], kv.first.data(), pb);
+      memcpy(&qs[(size_t)n_groups * qb], kv.first.data() + pb, qb);
+      memcpy(&gs[(size_t)n_groups * pb], kv.first.data() + pb + qb, pb);
+      ++n_groups;
+    }
+    std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * qb), valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    std::vector<uint32_t> idx(n), kgrp;
+    for (uint32_t i = 0; i < n; ++i) {
+      memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
+      memcpy(&sg[(size_t)i * 2 * qb], g[i]->th_b, 2 * (size_t)qb);
+      const uint32_t gi = gslot[group_key(g[i])];
+      std::string kk((const char*)&gi, 4);
+      kk.append((const char*)g[i]->th_y, pb);
+      auto ins = kslot.emplace(std::move(kk), (uint32_t)kslot.size());
+      if (ins.second) { ys.insert(ys.end(), g[i]->th_y, g[i]->th_y + pb); kgrp.push_back(gi); }
+      idx[i] = ins.first->second;
+    }
+    const int rc = dsa_verify_impl(lane.ctx, n, dg.data(), dlen, sg.data(), qb, idx.data(), (uint32_t)kslot.size(), ys.data(), kgrp.data(), pb, n_groups,
+                                   ps.data(), qs.data(), gs.data(), valid.data(), st.data(), false);
+    ++device_calls;
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(11) : st[i];
+      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
+    }
+  }
+
   void run_threshold(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const int kind = r0.kind;
+    if (kind == 11) { run_dsa_verify(lane, g, device_calls); return; }
     if (kind == 8) { run_ecdsa(lane, g, device_calls); return; }
     if (kind == 9) { run_ecdsa_verify(lane, g, device_calls); return; }
     if (kind == 10) { run_ecdsa_verify_keyset(lane, g, device_calls); return; }
@@ -924,6 +974,25 @@ int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint
   bftkv_gpu_batcher::Req r{10, keyset, nullptr, 0, nullptr, 0, false, 0};       // (an unknown handle fails its own group alone)
   r.th_shape = (uint64_t)10 | (uint64_t)dlen << 8;
   r.th_k = dlen; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
+  const int rc = b->submit(r);
+  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
+  if (rc) *valid_out = 0;
+  return rc;
+}
+
+int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, uint32_t qbytes, const uint8_t* y,
+                                 uint32_t pbytes, const uint8_t* p, const uint8_t* q, const uint8_t* g, uint8_t* valid_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (valid_out) *valid_out = 0;
+  if (!b || !status_out || !valid_out || !digest || !sig || !y || !p || !q || !g || dlen == 0 || dlen > 64 || qbytes == 0 || qbytes > 32 ||
+      pbytes == 0 || pbytes > 256)
+    return BFTKV_E_INVALID;
+  // what the batched entry refuses for the WHOLE call is refused here for this caller alone
+  if (!(p[pbytes - 1] & 1) || !(q[qbytes - 1] & 1)) return BFTKV_E_UNSUPPORTED;
+  bftkv_gpu_batcher::Req r{11, -4, nullptr, 0, nullptr, 0, false, 0};
+  r.th_shape = (uint64_t)11 | (uint64_t)dlen << 8 | (uint64_t)pbytes << 24 | (uint64_t)qbytes << 40;
+  r.th_k = dlen; r.th_nbytes = pbytes; r.th_qbytes = qbytes; r.th_a = digest; r.th_b = sig; r.th_mod = p; r.th_mod2 = q; r.th_g = g; r.th_y = y;
+  r.th_out = valid_out;
   const int rc = b->submit(r);
   *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
   if (rc) *valid_out = 0;

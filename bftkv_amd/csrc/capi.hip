@@ -35,6 +35,7 @@
 #include "kernels.hip"
 #include "threshold_kernels.hip"
 #include "ec_kernels.hip"
+#include "dsa_verify_kernels.hip"
 
 using namespace bftkv;
 
@@ -2304,6 +2305,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "rccl_capi.inc"
 #include "threshold_capi.inc"
 #include "ec_capi.inc"
+#include "dsa_verify_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

@@ -2,49 +2,58 @@
 // modular inverse by binary extended GCD (exact for ANY odd modulus, like math/big.ModInverse --
 // no primality assumption), modular multiplication by 8-word Montgomery products (double-and-add kept as the reference form), Horner reduction of a
 // 2128-bit radix-2^28 number.  Off the critical path: ~2 % of a DSA verification's work.
+// The same text compiles for the host (tests/c/dsa_verify_host.cpp), so everything is plain C++ behind U256_HD.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#ifndef U256_HD
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define U256_HD __host__ __device__ __forceinline__
+#else
+#define U256_HD static inline
+#endif
+#endif
 
 namespace bftkv {
 
 struct U256 { uint32_t w[8]; };
 
-__host__ __device__ __forceinline__ U256 u256_zero() { U256 r; for (int i = 0; i < 8; ++i) r.w[i] = 0; return r; }
-__host__ __device__ __forceinline__ bool u256_is_zero(const U256& a) { uint32_t o = 0; for (int i = 0; i < 8; ++i) o |= a.w[i]; return o == 0; }
-__host__ __device__ __forceinline__ bool u256_is_one(const U256& a) { uint32_t o = a.w[0] ^ 1u; for (int i = 1; i < 8; ++i) o |= a.w[i]; return o == 0; }
-__host__ __device__ __forceinline__ int u256_cmp(const U256& a, const U256& b) {
+U256_HD U256 u256_zero() { U256 r; for (int i = 0; i < 8; ++i) r.w[i] = 0; return r; }
+U256_HD bool u256_is_zero(const U256& a) { uint32_t o = 0; for (int i = 0; i < 8; ++i) o |= a.w[i]; return o == 0; }
+U256_HD bool u256_is_one(const U256& a) { uint32_t o = a.w[0] ^ 1u; for (int i = 1; i < 8; ++i) o |= a.w[i]; return o == 0; }
+U256_HD int u256_cmp(const U256& a, const U256& b) {
   int r = 0;
   for (int i = 0; i < 8; ++i) { if (a.w[i] != b.w[i]) r = a.w[i] < b.w[i] ? -1 : 1; }
   return r;   // the most significant differing word wins (loop runs LSW -> MSW)
 }
-__host__ __device__ __forceinline__ uint32_t u256_add(U256& a, const U256& b) {
+U256_HD uint32_t u256_add(U256& a, const U256& b) {
   uint64_t c = 0;
   for (int i = 0; i < 8; ++i) { c += (uint64_t)a.w[i] + b.w[i]; a.w[i] = (uint32_t)c; c >>= 32; }
   return (uint32_t)c;
 }
-__host__ __device__ __forceinline__ uint32_t u256_sub(U256& a, const U256& b) {
+U256_HD uint32_t u256_sub(U256& a, const U256& b) {
   uint64_t br = 0;
   for (int i = 0; i < 8; ++i) { uint64_t d = (uint64_t)a.w[i] - b.w[i] - br; a.w[i] = (uint32_t)d; br = (d >> 63) & 1; }
   return (uint32_t)br;
 }
-__host__ __device__ __forceinline__ void u256_shr1(U256& a, uint32_t top) {
+U256_HD void u256_shr1(U256& a, uint32_t top) {
   for (int i = 0; i < 7; ++i) a.w[i] = (a.w[i] >> 1) | (a.w[i + 1] << 31);
   a.w[7] = (a.w[7] >> 1) | (top << 31);
 }
-__host__ __device__ __forceinline__ uint32_t u256_shl1(U256& a) {
+U256_HD uint32_t u256_shl1(U256& a) {
   uint32_t c = a.w[7] >> 31;
   for (int i = 7; i > 0; --i) a.w[i] = (a.w[i] << 1) | (a.w[i - 1] >> 31);
   a.w[0] <<= 1;
   return c;
 }
-__host__ __device__ __forceinline__ int u256_bits(const U256& a) {
+U256_HD int u256_bits(const U256& a) {
   int b = 0;
   for (int i = 0; i < 8; ++i) if (a.w[i]) b = 32 * i + (32 - __builtin_clz(a.w[i]));
   return b;
 }
 // big-endian bytes -> U256; false when the value does not fit in 256 bits
-__host__ __device__ __forceinline__ bool u256_from_be(const uint8_t* p, uint32_t len, U256& out) {
+U256_HD bool u256_from_be(const uint8_t* p, uint32_t len, U256& out) {
   out = u256_zero();
   bool fits = true;
   for (uint32_t i = 0; i < len; ++i) {
@@ -56,22 +65,27 @@ __host__ __device__ __forceinline__ bool u256_from_be(const uint8_t* p, uint32_t
   return fits;
 }
 // (a + b) mod q for a, b < q
-__host__ __device__ __forceinline__ void u256_addmod(U256& a, const U256& b, const U256& q) {
+U256_HD void u256_addmod(U256& a, const U256& b, const U256& q) {
   uint32_t c = u256_add(a, b);
   if (c || u256_cmp(a, q) >= 0) u256_sub(a, q);
 }
 // a * b mod q, a < q (b arbitrary 256-bit)
-__host__ __device__ __forceinline__ U256 u256_mulmod(const U256& a, const U256& b, const U256& q) {
+U256_HD U256 u256_mulmod(const U256& a, const U256& b, const U256& q) {
   U256 r = u256_zero();
-  for (int i = 255; i >= 0; --i) {
-    uint32_t c = u256_shl1(r);
-    if (c || u256_cmp(r, q) >= 0) u256_sub(r, q);
-    if ((b.w[i >> 5] >> (i & 31)) & 1u) u256_addmod(r, a, q);
+#pragma unroll
+  for (int wi = 7; wi >= 0; --wi) {            // word by word, so that b is never indexed by a run-time value (registers, not scratch)
+    const uint32_t bw = b.w[wi];
+#pragma unroll 1
+    for (int i = 31; i >= 0; --i) {
+      uint32_t c = u256_shl1(r);
+      if (c || u256_cmp(r, q) >= 0) u256_sub(r, q);
+      if ((bw >> i) & 1u) u256_addmod(r, a, q);
+    }
   }
   return r;
 }
 // Montgomery product a*b*2^-256 mod q for odd q, a, b < q  (q0inv = -q^-1 mod 2^32); result < q
-__host__ __device__ __forceinline__ U256 u256_montmul(const U256& a, const U256& b, const U256& q, uint32_t q0inv) {
+U256_HD U256 u256_montmul(const U256& a, const U256& b, const U256& q, uint32_t q0inv) {
   uint32_t t[10];
 #pragma unroll
   for (int i = 0; i < 10; ++i) t[i] = 0;
@@ -94,7 +108,7 @@ __host__ __device__ __forceinline__ U256 u256_montmul(const U256& a, const U256&
   return r;
 }
 // a * b mod q for a, b < q through two Montgomery products (r2 = 2^512 mod q)
-__host__ __device__ __forceinline__ U256 u256_mulmod_mont(const U256& a, const U256& b, const U256& q, uint32_t q0inv, const U256& r2) {
+U256_HD U256 u256_mulmod_mont(const U256& a, const U256& b, const U256& q, uint32_t q0inv, const U256& r2) {
   return u256_montmul(u256_montmul(a, b, q, q0inv), r2, q, q0inv);
 }
 // s^-1 mod q for odd q > 1 and 0 < s < q; false when gcd(s, q) != 1 (math/big.ModInverse returns nil).
@@ -104,19 +118,19 @@ __host__ __device__ __forceinline__ U256 u256_mulmod_mont(const U256& a, const U
 // by selects -- u if u is even; else v if v is even; else the larger of the two, minus the other -- and halved; every
 // step removes a bit from bits(u)+bits(v), so 512 steps always suffice; the loop stops as soon as u (or, on the device,
 // every u of the wave) has reached 0.  gcd = v at that point.
-__host__ __device__ __forceinline__ U256 u256_select(bool c, const U256& a, const U256& b) {
+U256_HD U256 u256_select(bool c, const U256& a, const U256& b) {
   U256 r;
   for (int i = 0; i < 8; ++i) r.w[i] = c ? a.w[i] : b.w[i];
   return r;
 }
 // (x / 2) mod q for odd q: (x + (x odd ? q : 0)) >> 1
-__host__ __device__ __forceinline__ void u256_halfmod(U256& x, const U256& q) {
+U256_HD void u256_halfmod(U256& x, const U256& q) {
   const uint32_t odd = x.w[0] & 1u;
   uint64_t c = 0;
   for (int i = 0; i < 8; ++i) { c += (uint64_t)x.w[i] + (odd ? q.w[i] : 0u); x.w[i] = (uint32_t)c; c >>= 32; }
   u256_shr1(x, (uint32_t)c);
 }
-__host__ __device__ __forceinline__ bool u256_modinv_odd(const U256& s, const U256& q, U256& out) {
+U256_HD bool u256_modinv_odd(const U256& s, const U256& q, U256& out) {
   U256 u = s, v = q, x1 = u256_zero(), x2 = u256_zero();
   x1.w[0] = 1;
   for (int it = 0; it < 512; ++it) {

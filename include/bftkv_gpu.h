@@ -400,6 +400,14 @@ int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, 
  * that name it are in flight. */
 int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen,
                                           const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
+/* crypto/dsa.Verify (Go 1.13; the reference calls it as dsa.Verify(&priv.PublicKey, dgst[:orderSize], r, s), protocol/dist_test.go:93-96
+ * and crypto/threshold/dsa/dsa_test.go:317,456) for ONE signature: digest [dlen], sig [2 qbytes], y, p and g [pbytes], q [qbytes],
+ * *valid_out and *status_out as for bftkv_gpu_dsa_verify.  Callers are grouped by (pbytes, qbytes, dlen), whatever their groups and
+ * keys; an even p or q returns BFTKV_E_UNSUPPORTED for that caller alone, and a caller's fenced or invalid signature changes no one
+ * else's answer.  Whenever the return code is not 0, *status_out is BFTKV_TH_FAILED and *valid_out 0. */
+int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, uint32_t qbytes,
+                                 const uint8_t* y, uint32_t pbytes, const uint8_t* p, const uint8_t* q, const uint8_t* g, uint8_t* valid_out,
+                                 uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -578,6 +586,35 @@ int bftkv_gpu_ecdsa_verify(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* di
 int bftkv_gpu_ecdsa_verify_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
                                const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size,
                                uint8_t* valid_out, uint8_t* status_out);
+
+/* crypto/dsa.Verify of Go 1.13 on raw signatures -- what the reference asks of a finished threshold DSA signature,
+ * dsa.Verify(&priv.PublicKey, dgst[:orderSize], r, s) (protocol/dist_test.go:93-96, crypto/threshold/dsa/dsa_test.go:317,456) -- n_ops
+ * at once, groups and keys sent with the call:
+ *   digests [n_ops][dlen], 1 <= dlen <= 64: z = the digest as an integer, whole.  Go leaves truncation to the caller (the reference
+ *           truncates to the order's bytes before it calls), so a digest longer than bits(q) / 8 bytes is fenced, not answered;
+ *   sigs    [n_ops][2 qbytes]: r || s big-endian, as formatDSA writes them (crypto/threshold/dsa/dsa_core.go:375-387); qbytes <= 32;
+ *   keys_y  [n_keys][pbytes]: the public values (n_keys >= 1); key_group [n_keys] names each key's group, NULL means group 0; key_idx
+ *           [n_ops] picks a key per signature, NULL means key 0; an index past a table is clamped to its last entry;
+ *   p, g    [n_groups][pbytes], q [n_groups][qbytes] (n_groups >= 1, pbytes <= 256): p odd and at most 2048 bits, q odd.  Neither
+ *           is tested for primality, nor g for its order; g or y >= p (0 and p included) are reduced as big.Int.Exp reduces them;
+ *   valid_out [n_ops]: 1 where Verify returns true, else 0;
+ *   status_out [n_ops]: BFTKV_TH_OK (valid_out is Verify's answer: 0 for r or s outside [1, q), for a q whose bit length is no
+ *           multiple of 8, else whether g^u1 y^u2 mod p mod q = r);
+ *           BFTKV_TH_FENCED (valid_out 0, the reference decides): dlen > bits(q) / 8;
+ *           BFTKV_TH_NO_INVERSE (valid_out 0): s has no inverse mod a composite q -- ModInverse returns nil, which Go 1.13.0
+ *           dereferences and later patch releases answer with false; fenced wins over it (docs/parity.md, "DSA verification");
+ *           BFTKV_TH_FAILED whenever the return code is not 0 (the bytes start out as failures, valid_out as 0).
+ * n_ops = 0 returns 0; a NULL array, a zero count or a width out of range BFTKV_E_INVALID; a group with an even p or an even q
+ * BFTKV_E_UNSUPPORTED for the whole call.  The window tables of the call (b^1 .. b^15 per distinct g and y, 4.5 KB each) are
+ * built once per call: scratch grows with n_groups + n_keys, not with n_ops. */
+int bftkv_gpu_dsa_verify(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, uint32_t qbytes,
+                         const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys_y, const uint32_t* key_group, uint32_t pbytes,
+                         uint32_t n_groups, const uint8_t* p, const uint8_t* q, const uint8_t* g, uint8_t* valid_out, uint8_t* status_out);
+/* same with digests / sigs / key_idx / valid_out / status_out resident in HBM, asynchronous on the context's stream (keys_y,
+ * key_group, p, q and g stay host pointers, read before the call returns). */
+int bftkv_gpu_dsa_verify_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, uint32_t qbytes,
+                             const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys_y, const uint32_t* key_group, uint32_t pbytes,
+                             uint32_t n_groups, const uint8_t* p, const uint8_t* q, const uint8_t* g, uint8_t* valid_out, uint8_t* status_out);
 
 /* Resident key sets: the keys of bftkv_gpu_ecdsa_verify registered once, for callers whose keys outlive a call (the distributed CA
  * key of a threshold signature).  keys [n_keys][1 + 2 fbytes] elliptic.Marshal bytes, 1 <= n_keys <= 4096; curve, bit_size and

@@ -242,6 +242,43 @@ def ecdsa_verify_calls():
         note("batcher_ecdsa_verify", rc)
 
 
+def dsa_verify_calls():
+    """bftkv_gpu_dsa_verify, its _dev form (whose arrays must live in HBM: only where the call is refused before anything is
+    written, or has no operations) and the batcher entry: whatever comes back, a non-zero return leaves failures and no verdict."""
+    pb = rng.choice([0, 1, 64, 128, 256, 257, 384])
+    qb = rng.choice([0, 1, 20, 28, 32, 33])
+    n_ops = rng.choice([0, 0, 1, 2, 5, 64])
+    n_keys, n_groups = rng.choice([0, 1, 1, 2, 7]), rng.choice([0, 1, 1, 3])
+    dlen = rng.choice([0, 1, 20, 32, 64, 65, 4096])
+    dg, sg = buf(n_ops * min(dlen, 4096)), buf(n_ops * 2 * qb)
+    y, p, q, g = buf(max(n_keys, 1) * pb), buf(max(n_groups, 1) * pb), buf(max(n_groups, 1) * qb), buf(max(n_groups, 1) * pb)
+    if rng.random() < 0.7:                                  # odd moduli: the call reaches the kernels
+        for arr, w in ((p, pb), (q, qb)):
+            if w:
+                arr[w - 1::w] |= 1
+    ki = np.array([rng.choice([0, 1, n_keys, 2 ** 32 - 1]) for _ in range(max(n_ops, 1))], dtype=np.uint32)
+    kg = np.array([rng.choice([0, 1, n_groups, 2 ** 32 - 1]) for _ in range(max(n_keys, 1))], dtype=np.uint32)
+    kip = ki.ctypes.data_as(vp) if rng.random() < 0.5 else None
+    kgp = kg.ctypes.data_as(vp) if rng.random() < 0.5 else None
+    valid, st = buf(n_ops, "zero"), buf(n_ops, "zero")
+    which = rng.randrange(3)
+    if which == 0:
+        rc = lib.bftkv_gpu_dsa_verify(ctx, n_ops, p8(dg), dlen, p8(sg), qb, kip, n_keys, p8(y), kgp, pb, n_groups, p8(p), p8(q), p8(g), p8(valid), p8(st))
+        assert rc == 0 or (not valid[:n_ops].any() and (st[:n_ops] == 0xFF).all()), ("dsa_verify", rc)      # fail closed
+        note("dsa_verify", rc)
+    elif which == 1:
+        if rng.random() < 0.5:
+            n_ops = 0
+        note("dsa_verify_dev", lib.bftkv_gpu_dsa_verify_dev(ctx, n_ops, p8(dg), dlen, p8(sg), qb, kip, n_keys, p8(y), kgp, pb, n_groups, p8(p), p8(q),
+                                                            p8(g), None, None))      # (no output arrays: refused unless there is nothing to do)
+    else:
+        v1, s1 = C.c_uint8(0x55), C.c_uint8(0x55)
+        rc = lib.bftkv_gpu_batcher_dsa_verify(batcher, p8(buf(min(dlen, 4096))), dlen, p8(buf(2 * qb)), qb, p8(buf(pb)), pb, p8(p), p8(q), p8(g),
+                                              C.byref(v1), C.byref(s1))
+        assert rc == 0 or (s1.value == 0xFF and v1.value == 0), ("batcher_dsa_verify", rc, s1.value, v1.value)      # fail closed
+        note("batcher_dsa_verify", rc)
+
+
 def ecdsa_keyset_calls():
     """The key-set entries: create (any key bytes: a refused key does not refuse the set), info, the test hook, verification through
     the handle (host form, _dev form only where it is refused or has no operations, batcher) and destroy, with live, stale and
@@ -454,7 +491,7 @@ t0 = time.time()
 n = 0
 while time.time() - t0 < budget:
     rng.choice([threshold_batched, threshold_batched, threshold_one, verify_calls, verify_calls, keyring_and_quorum, cert_calls, cert_calls,
-                ecdsa_calls, ecdsa_verify_calls, ecdsa_keyset_calls])()
+                ecdsa_calls, ecdsa_verify_calls, ecdsa_keyset_calls, dsa_verify_calls])()
     n += 1
 lib.bftkv_gpu_batcher_destroy(batcher)
 lib.bftkv_gpu_destroy(ctx)

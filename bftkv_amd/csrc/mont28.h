@@ -7,9 +7,12 @@
 //   * lazy carries: every limb product is ONE v_mad_u64_u32 into a 64-bit column accumulator (152 products of < 2^56.6 fit
 //     in 64 bits).  Measured on MI355X (tools/microbench): a wave64 v_mad_u64_u32 holds a SIMD's issue port for 4.64 cycles,
 //     a 64-bit add or shift for ~4.3, a plain 32-bit op for 2.3 -- the multiplier is barely dearer than a carry, so the loop
-//     is written to issue as few non-MAC instructions as possible (5 per row, 2 per shifted column);
+//     is written to issue as few non-MAC instructions as possible (5 per row, 1 per shifted column);
 //   * row-wise (operand-scanning) Montgomery with a sliding window of 2L-1 columns per lane; after L rows the window has
-//     slid by exactly one lane and is re-aligned with DPP row_shl:1;
+//     slid by exactly one lane.  The 76- and 112-limb forms keep the window in a RING of 2L columns (two blocks of rows per
+//     loop iteration, at ring offsets 0 and L), so the slide moves nothing, and the limb that arrives from the next lane
+//     (DPP row_shl:1 of a column that lane has retired) is the ADDEND of the first MAC into the fresh column it belongs
+//     to -- no 64-bit add.  The 152-limb form re-aligns the window after every block, where it also normalises carries;
 //   * the broadcast operand a_i is read from LDS (same address across the group = broadcast), the per-row Montgomery
 //     factor m is computed by group lane 0 and broadcast with DPP quad_perm, the limb mask riding on that move;
 //   * squarings form one triangle of every limb-product block (mont_mul<.., SQR = true>).
@@ -84,6 +87,45 @@ __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {
   return (uint64_t)a * (uint64_t)b + c;   // -> v_mad_u64_u32
 }
 
+// One block of L rows of mont_mul (below) on the ring window: the forms without block-boundary normalisation.  Window column j of this block
+// is Q[(O + j) % 2L]; the next block runs at offset O + L, where its columns 0 .. L-2 already are.  Order within a row:
+//   row r > 0 first reads the limb the NEXT lane retired in row r-1 (its column r-1, low 28 bits: final since that row)
+//   and hands it to the MAC with b[L-1] as its addend -- that MAC is the first touch of the fresh column r+L-1, exactly
+//   the column the limb belongs to once the window has slid by a lane;
+//   row 0's fresh column L-1 holds its limb already: the previous block left it there after its last row (below), and
+//   before the first block it is 0.
+// Group lane TPI-1 reads the next group's lane 0, whose retired columns are zero by construction; the last lane of a DPP
+// row reads 0 through bound_ctrl.
+template <int L, int TPI, bool SQR, int O>
+__device__ __forceinline__ void mont_block_ring(uint64_t (&Q)[2 * L], const uint32_t* ap, const uint32_t (&b)[L],
+                                                const uint32_t (&n)[L], uint32_t n0inv, int qlane, uint32_t mask_v) {
+  constexpr int M = 2 * L;
+#pragma unroll
+  for (int r = 0; r < L; ++r) {
+    const uint32_t ai = ap[r];
+    const uint32_t ai2 = ai << 1;      // SQR: off-diagonal products count twice (limbs <= 2^28: the product stays < 2^57)
+    uint64_t in = 0;
+    if (r > 0) in = dpp_row_shl1((uint32_t)Q[(O + r - 1) % M]) & mask_v;   // v_and_b32_dpp; the high half stays 0
+    // Q[r+k] += a_i * b[k]
+#pragma unroll
+    for (int k = SQR ? r : 0; k < L; ++k) {
+      const uint32_t av = (SQR && k > r) ? ai2 : ai;
+      if (k == L - 1 && r > 0) Q[(O + r + k) % M] = mad64(av, b[k], in);   // first touch of a fresh column
+      else Q[(O + r + k) % M] = mad64(av, b[k], Q[(O + r + k) % M]);
+    }
+    // Montgomery factor from group lane 0's column r
+    const uint32_t m = grp_bcast0<TPI>((uint32_t)Q[(O + r) % M] * n0inv, qlane) & mask_v;
+#pragma unroll
+    for (int k = 0; k < L; ++k) Q[(O + r + k) % M] = mad64(m, n[k], Q[(O + r + k) % M]);
+    // retire column r: push its carry into column r+1.  What stays behind is the column's low 28 bits (zero in group
+    // lane 0 by construction); the mask is applied where the previous lane reads them, in its next row.
+    Q[(O + r + 1) % M] += Q[(O + r) % M] >> MONT_W;
+  }
+  // the limb retired by the last row: column L-1 of the next block (the addend of its row 0, k = L-1 MAC), or the top
+  // limb of the result
+  Q[(O + M - 1) % M] = dpp_row_shl1((uint32_t)Q[(O + L - 1) % M]) & mask_v;
+}
+
 // out = a * b * R^-1 mod n, value < 2n, limbs "lazily normal": every limb <= 2^28.
 //   a_lds : this number's N limbs of operand a in LDS (all 4 lanes of the quad pass the same pointer)
 //   b, n  : this lane's L limbs (lane l of the quad holds limbs [l*L, l*L+L))
@@ -107,43 +149,46 @@ __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_l
   // A column receives up to 2N = 2*TPI*L products of < 2^56: up to 255 of them fit 64 bits (76 and 112 limbs); beyond
   // that (152 limbs) the live columns are carry-normalised at every block boundary.
   constexpr bool NORM = 2 * TPI * L > 255;
+  static_assert(TPI % 2 == 0, "the ring window runs two blocks per loop iteration");
   uint32_t mask_v;   // the limb mask in a VGPR: lets the Montgomery factor's mask carry the quad broadcast (v_and_b32_dpp)
   asm("v_mov_b32 %0, 0xfffffff" : "=v"(mask_v));
-  uint64_t Q[2 * L - 1];
+  uint64_t Q[NORM ? 2 * L - 1 : 2 * L];   // the ring, or (NORM) a window of 2L-1 columns
 #pragma unroll
   for (int k = 0; k < L + (NORM ? 1 : 0); ++k) Q[k] = 0;
 
+  if constexpr (!NORM) {
+    // TPI is even, so the last block runs at offset L and leaves the result in Q[0 .. L-1]
 #pragma unroll 1
-  for (int blk = 0; blk < TPI; ++blk) {
-    const uint32_t* ap = a_lds + blk * L;
+    for (int blk = 0; blk < TPI; blk += 2) {
+      mont_block_ring<L, TPI, SQR, 0>(Q, a_lds + blk * L, b, n, n0inv, qlane, mask_v);
+      mont_block_ring<L, TPI, SQR, L>(Q, a_lds + (blk + 1) * L, b, n, n0inv, qlane, mask_v);
+    }
+  } else {
+#pragma unroll 1
+    for (int blk = 0; blk < TPI; ++blk) {
+      const uint32_t* ap = a_lds + blk * L;
 #pragma unroll
-    for (int r = 0; r < L; ++r) {
-      const uint32_t ai = ap[r];
-      const uint32_t ai2 = ai << 1;      // SQR: off-diagonal products count twice (limbs <= 2^28: the product stays < 2^57)
-      // Q[r+k] += a_i * b[k]
+      for (int r = 0; r < L; ++r) {
+        const uint32_t ai = ap[r];
+        const uint32_t ai2 = ai << 1;
+        // Q[r+k] += a_i * b[k]
 #pragma unroll
-      for (int k = SQR ? r : 0; k < L; ++k) {
-        const uint32_t av = (SQR && k > r) ? ai2 : ai;
-        if (k == L - 1 && r > 0) Q[r + k] = mad64(av, b[k], (NORM && r == 1) ? Q[r + k] : 0);   // first touch of a fresh column
-        else Q[r + k] = mad64(av, b[k], Q[r + k]);
+        for (int k = SQR ? r : 0; k < L; ++k) {
+          const uint32_t av = (SQR && k > r) ? ai2 : ai;
+          if (k == L - 1 && r > 0) Q[r + k] = mad64(av, b[k], (r == 1) ? Q[r + k] : 0);   // first touch of a fresh column; L holds the seed
+          else Q[r + k] = mad64(av, b[k], Q[r + k]);
+        }
+        const uint32_t m = grp_bcast0<TPI>((uint32_t)Q[r] * n0inv, qlane) & mask_v;
+#pragma unroll
+        for (int k = 0; k < L; ++k) Q[r + k] = mad64(m, n[k], Q[r + k]);
+        Q[r + 1] += Q[r] >> MONT_W;
       }
-      // Montgomery factor from quad lane 0's column r
-      const uint32_t m = grp_bcast0<TPI>((uint32_t)Q[r] * n0inv, qlane) & mask_v;
+      // window slid by L columns = one lane: re-align.  new Q[k] = own Q[L+k] + next lane's Q[k]
 #pragma unroll
-      for (int k = 0; k < L; ++k) Q[r + k] = mad64(m, n[k], Q[r + k]);
-      // retire column r: push its carry into column r+1.  What stays behind is the column's low 28 bits (zero in quad
-      // lane 0 by construction); the mask is applied where they are next read, the window shift below.
-      Q[r + 1] += Q[r] >> MONT_W;
-    }
-    // window slid by L columns = one lane: re-align.  new Q[k] = own Q[L+k] + next lane's Q[k]
-    // (quad lane 3 reads the next quad's lane 0, whose low columns are all zero; the last lane of
-    //  a DPP row reads 0 through bound_ctrl).
-#pragma unroll
-    for (int k = 0; k < L; ++k) {
-      const uint64_t nx = dpp_row_shl1((uint32_t)Q[k]) & mask_v;   // the retired column's low 28 bits: v_and_b32_dpp
-      Q[k] = (k < L - 1) ? Q[L + k] + nx : nx;
-    }
-    if (NORM) {
+      for (int k = 0; k < L; ++k) {
+        const uint64_t nx = dpp_row_shl1((uint32_t)Q[k]) & mask_v;   // the retired column's low 28 bits: v_and_b32_dpp
+        Q[k] = (k < L - 1) ? Q[L + k] + nx : nx;
+      }
       // carry-normalise the live columns; the top carry seeds column L (accumulated by the next first touch)
 #pragma unroll
       for (int k = 0; k < L; ++k) {

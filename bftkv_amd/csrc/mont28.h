@@ -146,8 +146,12 @@ template <int L, int TPI = MONT_TPI, bool SQR = false>
 __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_lds,
                                          const uint32_t (&b)[L], const uint32_t (&n)[L],
                                          uint32_t n0inv, int qlane) {
-  // A column receives up to 2N = 2*TPI*L products of < 2^56: up to 255 of them fit 64 bits (76 and 112 limbs); beyond
-  // that (152 limbs) the live columns are carry-normalised at every block boundary.
+  // A column is in a lane's window for L rows and receives one a*b and one m*n product from each: 2L products of at most
+  // 2^56 (a squaring's doubled terms are 2^57, and half as many), plus the carry of the column retired before it.  Measured
+  // on a model with unbounded integers (tests/test_mont_model.py): at most 38.0 * 2^56 = 0.148 * 2^64
+  // for L = 19 with every limb and every Montgomery factor at its maximum, in the ring forms and in the normalising one
+  // alike -- NOT the 2N = 2*TPI*L products this comment used to count, of which 255 would fit.  The switch below still
+  // follows that older count: the 152-limb form carry-normalises its live columns at every block boundary.
   constexpr bool NORM = 2 * TPI * L > 255;
   static_assert(TPI % 2 == 0, "the ring window runs two blocks per loop iteration");
   uint32_t mask_v;   // the limb mask in a VGPR: lets the Montgomery factor's mask carry the quad broadcast (v_and_b32_dpp)

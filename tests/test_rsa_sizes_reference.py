@@ -88,3 +88,32 @@ def test_matrix_is_what_it_claims_and_the_oracles_agree():
     assert sum(fenced) == sum(1 for c in cases if c.bits > RS.MAX_BITS) + sum(1 for c in cases if c.over_cap and c.fits)
     assert all(st == (RS.ST_OK if c.fits else RS.ST_BAD_SIG) for c, st in zip(cases, status) if c.over_cap)
     assert sum(1 for c in cases if c.over_cap and not c.fits) >= 20
+
+
+def test_oracles_agree_under_extremal_prime_moduli():
+    """The keys of tests/extremal_keys.py (prime moduli with every limb full / almost every limb zero, e = 65537, 3 and 17) in
+    the value shapes of cell_cases: Python integers and OpenSSL bignums give every case the same status, the untouched signature
+    is accepted in every (key, hash) cell and every wrong value refused.  If the C oracle refuses a prime modulus the assertion
+    on its trace says so."""
+    from tests import extremal_keys as X
+    keys, cases = X.rsa_keys(), X.rsa_cases()
+    assert len(keys) == 14 and all(RS.size_class(kp.n.bit_length()) is not None for kp in keys)
+    ring = [RS.entity(kp) for kp in keys]
+    co = COracle()
+    co.set_keyring(col.Keyring(keyring=ring))
+    tally = Counter()
+    for c in cases:
+        st = RS.oracle_status(ring, c)
+        tr, nv, err = co.trace_item(c.tbs, c.sig)
+        assert tr == [st] and nv == (1 if st == RS.ST_OK else 0), "the C oracle differs: %r" % ((c.bits, keys[c.key].name, c.hash_id, c.variant, st, tr),)
+        assert c.fits
+        tally[(c.key, c.hash_id, c.variant, st)] += 1
+    congruent = ["untouched", "canonical mpi", "at the cap", "over the cap"]
+    for ki in range(len(keys)):
+        for hash_id, _ in RS.HASHES:
+            for v in congruent:
+                assert tally[(ki, hash_id, v, RS.ST_OK)] == 1, (keys[ki].name, hash_id, v)
+            assert tally[(ki, hash_id, "s + n", RS.ST_OK)] + tally[(ki, hash_id, "s + n, long", RS.ST_OK)] == 1
+            assert tally[(ki, hash_id, "bit flipped", RS.ST_BAD_SIG)] == 1
+            assert sum(n for (k, h, v, st), n in tally.items() if (k, h) == (ki, hash_id) and v.startswith("em ") and st == RS.ST_BAD_SIG) == 1
+    assert sum(tally.values()) == len(cases) == 14 * 5 * 7

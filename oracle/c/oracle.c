@@ -583,7 +583,8 @@ static int check_detached(const oracle* o, const uint8_t* tbs, uint64_t tbs_len,
       if (k->key_id != s.issuer || !k->usable_sign) continue;
       /* VerifySignature appends the suffix to the shared hash on every candidate */
       if (k->pk_algo == 2 || k->pk_algo == 16) { st = ST_KEY_CANNOT_SIGN; continue; }   /* checked before the hash is touched */
-      uint8_t trailer[6] = {4, 0xFF, 0, 0, (uint8_t)(s.prefix_len >> 8), (uint8_t)s.prefix_len};
+      /* the length is 6 + hl: beyond 16 bits once hl reaches 65,530 */
+      uint8_t trailer[6] = {4, 0xFF, (uint8_t)(s.prefix_len >> 24), (uint8_t)(s.prefix_len >> 16), (uint8_t)(s.prefix_len >> 8), (uint8_t)s.prefix_len};
       h_update(&hc, s.prefix, s.prefix_len);
       if (!s.v3) h_update(&hc, trailer, 6);            /* VerifySignatureV3: type || creation time only */
       uint8_t dg[64];

@@ -330,7 +330,9 @@ def test_malformed_and_edge_streams(gpu_ctx, exit_mode):
     tbs_l, ss_l = [], []
     pub = cl.replicas[0].entity[:280]                                   # a well-formed public-key packet (tag 6)
     for i in range(64):
-        ln = [0, 1, 55, 56, 57, 63, 64, 65, 119, 120, 127, 128, 200, 1000][i % 14]   # SHA-256 padding boundaries
+        # payload lengths around the block size -- NOT padding boundaries: the hashed stream is the payload and a 28-byte suffix, so
+        # a 55-byte payload finishes at rem = 83.  The boundaries themselves are aimed at in tests/test_gpu_hash_finish.py
+        ln = [0, 1, 55, 56, 57, 63, 64, 65, 119, 120, 127, 128, 200, 1000][i % 14]
         tbs = rng.bytes(ln)
         sigs = [cb.detach_sign(r, tbs) for r in cl.replicas]
         k = i % 16

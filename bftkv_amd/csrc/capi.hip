@@ -70,7 +70,8 @@ struct DevBuf {
 struct KeyEntry {
   uint64_t key_id = 0, entity_id = 0;
   uint8_t algo = 0, flags = 0;
-  uint32_t bits = 0, e = 0, n0 = 0, qbits = 0;
+  uint32_t bits = 0, e = 0, n0 = 0, qbits = 0, n0_29 = 0;
+  std::vector<uint32_t> nl29, r2_29;    // <= 2048-bit RSA: n and (2^2088)^2 mod n as 72 limbs of 29 bits, with n0_29 = -n^-1 mod 2^29 (k_rsa_modexp<18,4,29>)
   std::vector<uint32_t> nl, r2, r2w, qw, dtab, qpow, qconst;    // r2w: R^2 mod n for the 80-limb form (<= 2048-bit RSA); qpow: 2^(28 j) mod q rows, qconst: mod-q Montgomery constants (DSA)
   std::string material;
   bool cert_only = false;
@@ -132,6 +133,7 @@ struct bftkv_gpu_ctx {
   uint32_t n_ring_entities = 0;
   std::map<std::string, bool> cert_valid;   // certificate bytes -> openpgp.ReadEntity would accept it
   DevBuf k_r2w;
+  DevBuf k_n29, k_r2_29, k_n0_29;
   DevBuf k_id, k_entity, k_algo, k_flags, k_bits, k_e, k_n, k_r2, k_n0, k_q, k_qbits, k_dsatab, k_dsaslot, k_sorted_id, k_sorted_slot;
   // fixed-base DSA tables: built once per distinct key material, kept across key-table uploads
   DevBuf dsa_comb;
@@ -223,7 +225,7 @@ struct bftkv_gpu_ctx {
                                             // in the runtime's hands when one completes (a pageable copy call returns when it is done)
   std::vector<hipEvent_t> hb_ev;            // [2k] signature streams of piece k on the device, [2k + 1] its payloads
   uint8_t* hb_out = nullptr; size_t hb_out_cap = 0;   // pinned: per-piece results land here, copied to the caller after the last sync
-  // Unused dynamic LDS added to every k_rsa_modexp<19,4> launch of this context: 38.9 KB + pad > 53 KB leaves room for two blocks
+  // Unused dynamic LDS added to every 4-lane k_rsa_modexp launch of this context: 36.9 KB (18 x 4 at 2^29; 19 x 4: 38.9 KB) + pad > 53 KB leaves room for two blocks
   // per CU instead of three, i.e. 2 waves per SIMD and 192 of the 512 VGPRs free -- room in which the walk / parse / hash / tally
   // kernels of OTHER calls (or pieces) start at once instead of waiting for a round of modexp blocks to retire.
   uint32_t modexp_lds_pad = 0;
@@ -476,6 +478,7 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   if (!c->chunk_ctr.p) { HIPCHK(c, c->chunk_ctr.ensure(16)); HIPCHK(c, hipMemsetAsync(c->chunk_ctr.p, 0, 16, c->stream)); }
   HIPCHK(c, c->chunk_arena.ensure(CHUNK_ARENA_MIN + (staged_cap ? 2 * (size_t)ss_len : 0)));
   HIPCHK(c, c->pk_count.ensure(96));   // [0..3] work-list lengths, [4] some signature uses a hash other than SHA-256,
+                                       // [5] some RSA value is too long for the 29-bit form (SIGF_WIDE_VALUE),
                                        // [8..11] lengths after phase 1 (phase 2's start), [12..15] zeros (phase 1's start),
                                        // [16..19] two uint64: clock stamps of k_rsa_modexp (bftkv_gpu_last_sclk_mhz)
   if (plan_q) HIPCHK(c, c->plan_cut.ensure(sizeof(uint32_t) * (size_t)n_items + 16));
@@ -623,9 +626,20 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     if (wide8)
       hipLaunchKernelGGL((k_rsa_modexp<10, MONT_TPI_BIG>), qg8, dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
                          cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
-    else
-    hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                       cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
+    else {
+#if BFTKV_RSA_FORM == 29
+      // 18 x 4 limbs of 29 bits (2 x 64 x 72 x 4 B of LDS per block), and right behind it the 19 x 4 form of 28 bits for the
+      // values too long for 72 limbs (262 .. 266 bytes; k_parse_body flags them and raises cnt_p[5]): normally a grid of
+      // blocks that read one word and return
+      hipLaunchKernelGGL((k_rsa_modexp<RSA29_L, MONT_TPI, RSA29_W>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16), (const uint32_t*)(cnt_p + 5));
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI, MONT_W, true>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr, (const uint32_t*)(cnt_p + 5));
+#else
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
+#endif
+    }
     // larger moduli: only when the keyring holds such keys (blocks beyond the queued count exit at once)
     if (c->have_rsa3072)
       hipLaunchKernelGGL((k_rsa_modexp<MONT_L3072, MONT_TPI_BIG>), qg8, dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
@@ -767,7 +781,7 @@ int make_key_entry(bftkv_gpu_ctx* c, const bftkv_gpu_pubkey& k, bool cert_only, 
   if (cert_only) e.flags |= KEYF_CERT_ONLY;
   e.bits = (uint32_t)hostbn::bit_length(k.n, k.n_len);
   e.e = 0; e.n0 = 0; e.qbits = 0;
-  e.r2w.clear();
+  e.r2w.clear(); e.nl29.clear(); e.r2_29.clear(); e.n0_29 = 0;
   e.nl.assign(MONT_NMAX, 0); e.r2.assign(MONT_NMAX, 0); e.qw.assign(8, 0); e.dtab.assign(2 * DSA_N_BIG, 0); e.qpow.clear(); e.qconst.clear();
   if (k.pk_algo == PK_RSA || k.pk_algo == PK_RSA_SIGN_ONLY) {
     if (hostbn::bit_length(k.e, k.e_len) > 32) return fail(c, BFTKV_E_UNSUPPORTED, "RSA public exponent wider than 32 bits");  // x/crypto refuses > 24 bits
@@ -781,6 +795,8 @@ int make_key_entry(bftkv_gpu_ctx* c, const bftkv_gpu_pubkey& k, bool cert_only, 
       uint32_t n0b = 0;
       e.r2w.assign(80, 0);
       (void)hostbn::mont_setup(k.n, k.n_len, 80, nl80.data(), e.r2w.data(), &n0b);
+      e.nl29.assign(RSA29_N, 0); e.r2_29.assign(RSA29_N, 0);              // the 4-lane form of big calls: 72 limbs of 29 bits
+      (void)hostbn::mont_setup(k.n, k.n_len, RSA29_N, e.nl29.data(), e.r2_29.data(), &e.n0_29, RSA29_W);
     }
   } else if (k.pk_algo == PK_DSA) {
     // n = p, e = q.  Montgomery domain mod p; g and y in Montgomery form seed the fixed-base tables.
@@ -1035,8 +1051,13 @@ int upload_key_table(bftkv_gpu_ctx* c) {
   if (c->root) return fail(c, BFTKV_E_STATE, "a forked context cannot change the key table (use its root)");
   KtWrite kw(c);      // the forks' calls in flight drain first; new ones wait
   std::vector<uint64_t> key_id, entity_ids;
-  std::vector<uint32_t> entity, bits, e32, nl, r2, r2w, n0, qw, qbits, dtab;
+  std::vector<uint32_t> entity, bits, e32, nl, r2, r2w, n0, qw, qbits, dtab, nl29, r2_29, n0_29;
   std::vector<uint8_t> algo, flags;
+  auto add29 = [&](const KeyEntry& e) {     // rows of the 29-bit tables: zero for keys that have none
+    nl29.insert(nl29.end(), e.nl29.begin(), e.nl29.end()); nl29.resize(key_id.size() * RSA29_N, 0);
+    r2_29.insert(r2_29.end(), e.r2_29.begin(), e.r2_29.end()); r2_29.resize(key_id.size() * RSA29_N, 0);
+    n0_29.push_back(e.n0_29);
+  };
   std::vector<const KeyEntry*> rows;
   auto add = [&](const KeyEntry& e, bool own_entity) {
     uint32_t ent = 0;
@@ -1049,6 +1070,7 @@ int upload_key_table(bftkv_gpu_ctx* c) {
     bits.push_back(e.bits); e32.push_back(e.e); n0.push_back(e.n0); qbits.push_back(e.qbits);
     nl.insert(nl.end(), e.nl.begin(), e.nl.end()); r2.insert(r2.end(), e.r2.begin(), e.r2.end());
     r2w.insert(r2w.end(), e.r2w.begin(), e.r2w.end()); r2w.resize(key_id.size() * 80, 0);
+    add29(e);
     qw.insert(qw.end(), e.qw.begin(), e.qw.end()); dtab.insert(dtab.end(), e.dtab.begin(), e.dtab.end());
     rows.push_back(&e);
     return ent;
@@ -1066,6 +1088,7 @@ int upload_key_table(bftkv_gpu_ctx* c) {
       bits.push_back(e.bits); e32.push_back(e.e); n0.push_back(e.n0); qbits.push_back(e.qbits);
       nl.insert(nl.end(), e.nl.begin(), e.nl.end()); r2.insert(r2.end(), e.r2.begin(), e.r2.end());
       r2w.insert(r2w.end(), e.r2w.begin(), e.r2w.end()); r2w.resize(key_id.size() * 80, 0);
+      add29(e);
       qw.insert(qw.end(), e.qw.begin(), e.qw.end()); dtab.insert(dtab.end(), e.dtab.begin(), e.dtab.end());
       rows.push_back(&e);
     }
@@ -1086,9 +1109,11 @@ int upload_key_table(bftkv_gpu_ctx* c) {
   if ((rc = upload(c, c->k_id, key_id)) || (rc = upload(c, c->k_entity, entity)) || (rc = upload(c, c->k_algo, algo)) ||
       (rc = upload(c, c->k_flags, flags)) || (rc = upload(c, c->k_bits, bits)) || (rc = upload(c, c->k_e, e32)) ||
       (rc = upload(c, c->k_n, nl)) || (rc = upload(c, c->k_r2, r2)) || (rc = upload(c, c->k_n0, n0)) ||
-      (rc = upload(c, c->k_q, qw)) || (rc = upload(c, c->k_qbits, qbits)) || (rc = upload(c, c->k_dsatab, dtab)) || (rc = upload(c, c->k_r2w, r2w)))
+      (rc = upload(c, c->k_q, qw)) || (rc = upload(c, c->k_qbits, qbits)) || (rc = upload(c, c->k_dsatab, dtab)) || (rc = upload(c, c->k_r2w, r2w)) ||
+      (rc = upload(c, c->k_n29, nl29)) || (rc = upload(c, c->k_r2_29, r2_29)) || (rc = upload(c, c->k_n0_29, n0_29)))
     return rc;
   c->kt.r2_limbs80 = c->k_r2w.as<uint32_t>();
+  c->kt.n_limbs29 = c->k_n29.as<uint32_t>(); c->kt.r2_limbs29 = c->k_r2_29.as<uint32_t>(); c->kt.n0inv29 = c->k_n0_29.as<uint32_t>();
   c->n_keys = (uint32_t)key_id.size();
   c->kt.n_keys = c->n_keys;
   c->kt.n_limbs = c->k_n.as<uint32_t>();
@@ -1244,7 +1269,7 @@ void bftkv_gpu_destroy(bftkv_gpu_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   (void)hipStreamSynchronize(c->stream_h);
   (void)hipStreamSynchronize(c->stream_d);
-  for (DevBuf* b : {&c->k_id, &c->k_entity, &c->k_algo, &c->k_flags, &c->k_bits, &c->k_e, &c->k_n, &c->k_r2, &c->k_n0, &c->k_q, &c->k_qbits, &c->k_dsatab, &c->k_dsaslot, &c->dsa_comb, &c->k_sorted_id, &c->k_sorted_slot, &c->k_r2w,
+  for (DevBuf* b : {&c->k_id, &c->k_entity, &c->k_algo, &c->k_flags, &c->k_bits, &c->k_e, &c->k_n, &c->k_r2, &c->k_n0, &c->k_q, &c->k_qbits, &c->k_dsatab, &c->k_dsaslot, &c->dsa_comb, &c->k_sorted_id, &c->k_sorted_slot, &c->k_r2w, &c->k_n29, &c->k_r2_29, &c->k_n0_29,
                     &c->chunk_arena, &c->chunk_ctr, &c->counts, &c->base, &c->total, &c->item_flags, &c->walk_scratch, &c->cert_ent, &c->sig_class, &c->mid, &c->mid64, &c->hash_mask, &c->recs, &c->digests, &c->r, &c->xr,
                     &c->pk_list, &c->pk_list3072, &c->pk_list4096, &c->r3072, &c->r4096, &c->pk_count, &c->dsa_list, &c->dsa_u, &c->dsa_idx, &c->ids_tmp, &c->o_err, &c->o_nver, &c->o_verdict, &c->o_fenced, &c->in_tbs, &c->in_tbs_off,
                     &c->in_ss, &c->in_ss_off, &c->in_prefix, &c->in_prefix_off, &c->in_shared, &c->in_shared_off, &c->in_seg, &c->st_tmp, &c->item_tmp, &c->bits_tmp, &c->plan_cut, &c->txt_mid32, &c->txt_mid64, &c->txt_tail, &c->txt_len})

@@ -43,7 +43,7 @@ struct SigRec {
   uint8_t hash_tag[2];
   uint8_t pk_algo, hash_id, sig_type, status;
   uint8_t after_tag;      // status once the hash tag has matched; AFTER_TAG_PUBKEY: the public-key operation decides
-  uint8_t flags;          // bit0: signature value may be >= 2^(8k) (no x-shortcut in the exponent ladder)
+  uint8_t flags;          // bit0: signature value may be >= 2^(8k) (no x-shortcut in the exponent ladder); SIGF_* in kernels.hip
   uint8_t q_kind1;        // 1 + public-key work list the record belongs on (0: none) -- set by the parse, never by the hash stream
   uint8_t queued;         // the record has been put on that list (k_parse_body directly, or k_plan in two-phase calls)
   uint32_t pk_idx;        // index in the public-key work list
@@ -66,6 +66,10 @@ struct KeyTableDev {
   const uint32_t* r2_limbs;   // [n_keys][76] R^2 mod n
   const uint32_t* r2_limbs80; // [n_keys][80] (2^2240)^2 mod n: the 8-lane form of k_rsa_modexp for small calls (<= 2048-bit RSA keys)
   const uint32_t* n0inv;      // [n_keys] -n^-1 mod 2^28
+  // k_rsa_modexp<18,4,29>, the form of big calls for RSA keys of at most 2048 bits (zero rows otherwise): radix 2^29, R = 2^2088
+  const uint32_t* n_limbs29;  // [n_keys][72] modulus
+  const uint32_t* r2_limbs29; // [n_keys][72] (2^2088)^2 mod n
+  const uint32_t* n0inv29;    // [n_keys] -n^-1 mod 2^29
   // DSA keys only (zero otherwise)
   const uint32_t* q_words;    // [n_keys][8] subgroup order q, little-endian 32-bit words
   const uint32_t* q_bits;     // [n_keys]

@@ -55,36 +55,37 @@ inline void dbl_mod(uint32_t* a, const uint32_t* m, int n) {
   if (cmp(a, m, n) >= 0) sub(a, m, n);
 }
 
-// 32-bit words -> radix-2^28 limbs
-inline void to_limbs28(const uint32_t* w, int nwords, uint32_t* limbs, int nlimbs) {
+// 32-bit words -> radix-2^W limbs
+inline void to_limbs(const uint32_t* w, int nwords, uint32_t* limbs, int nlimbs, int W) {
   for (int j = 0; j < nlimbs; ++j) {
-    uint32_t bit = 28u * j, wi = bit >> 5, sh = bit & 31;
+    uint32_t bit = (uint32_t)W * j, wi = bit >> 5, sh = bit & 31;
     uint64_t v = 0;
     if ((int)wi < nwords) v = w[wi];
     if ((int)wi + 1 < nwords) v |= (uint64_t)w[wi + 1] << 32;
-    limbs[j] = (uint32_t)(v >> sh) & MASK28;
+    limbs[j] = (uint32_t)(v >> sh) & ((1u << W) - 1);
   }
 }
+inline void to_limbs28(const uint32_t* w, int nwords, uint32_t* limbs, int nlimbs) { to_limbs(w, nwords, limbs, nlimbs, W28); }
 
-// Montgomery constants for an odd modulus n < 2^(28*nlimbs - 2).
-//   r2[] = (2^(28*nlimbs))^2 mod n as limbs, n0inv = -n^-1 mod 2^28.  false if n is even or zero.
+// Montgomery constants for an odd modulus n < 2^(W*nlimbs - 2), limbs of W bits (28, or 29 for k_rsa_modexp<18,4,29>).
+//   r2[] = (2^(W*nlimbs))^2 mod n as limbs, n0inv = -n^-1 mod 2^W.  false if n is even or zero.
 // This form doubles 1 up to 2^(2*28*nlimbs) a bit at a time (4,256 passes for a 2048-bit modulus: 0.25 ms); mont_setup below gives
 // the same numbers in a few dozen microseconds and is what the library calls.  Kept as the definition the CPU suite checks it against.
 inline bool mont_setup_by_doubling(const uint8_t* n_be, uint32_t n_len, int nlimbs, uint32_t* n_limbs, uint32_t* r2_limbs,
-                                   uint32_t* n0inv) {
-  const int nwords = (28 * nlimbs + 31) / 32 + 1;
+                                   uint32_t* n0inv, int W = W28) {
+  const int nwords = (W * nlimbs + 31) / 32 + 1;
   std::vector<uint32_t> n(nwords), r(nwords);
   from_be(n_be, n_len, n.data(), nwords);
   if ((n[0] & 1) == 0) return false;
   r.assign(nwords, 0);
   r[0] = 1;
   if (cmp(r.data(), n.data(), nwords) >= 0) { r[0] = 0; }  // n == 1
-  for (int i = 0; i < 2 * 28 * nlimbs; ++i) dbl_mod(r.data(), n.data(), nwords);
-  to_limbs28(n.data(), nwords, n_limbs, nlimbs);
-  to_limbs28(r.data(), nwords, r2_limbs, nlimbs);
+  for (int i = 0; i < 2 * W * nlimbs; ++i) dbl_mod(r.data(), n.data(), nwords);
+  to_limbs(n.data(), nwords, n_limbs, nlimbs, W);
+  to_limbs(r.data(), nwords, r2_limbs, nlimbs, W);
   uint32_t n0 = n[0], inv = n0;            // inv = n0^-1 mod 2^32 by Newton iteration
   for (int i = 0; i < 5; ++i) inv *= 2u - n0 * inv;
-  *n0inv = (0u - inv) & MASK28;
+  *n0inv = (0u - inv) & ((1u << W) - 1);
   return true;
 }
 
@@ -134,15 +135,16 @@ inline void montmul64(const uint64_t* a, const uint64_t* b, const uint64_t* m, u
 // Montgomery constants for an odd modulus n < 2^(28*nlimbs - 2): the numbers of mont_setup_by_doubling (tests/test_host_arith.py
 // compares the two word for word), computed as 2^(2*28*nlimbs) mod n by square-and-double in a host-side Montgomery domain of
 // R' = 2^(64k) just above n: R' mod n by doubling up from the modulus' top bit (at most 65 times), then 13 squarings.
-inline bool mont_setup(const uint8_t* n_be, uint32_t n_len, int nlimbs, uint32_t* n_limbs, uint32_t* r2_limbs, uint32_t* n0inv) {
-  const int nwords = (28 * nlimbs + 31) / 32 + 1;
+inline bool mont_setup(const uint8_t* n_be, uint32_t n_len, int nlimbs, uint32_t* n_limbs, uint32_t* r2_limbs, uint32_t* n0inv,
+                       int W = W28) {
+  const int nwords = (W * nlimbs + 31) / 32 + 1;
   std::vector<uint32_t> n(nwords);
   from_be(n_be, n_len, n.data(), nwords);
   if ((n[0] & 1) == 0) return false;
-  to_limbs28(n.data(), nwords, n_limbs, nlimbs);
+  to_limbs(n.data(), nwords, n_limbs, nlimbs, W);
   uint32_t n0 = n[0], inv = n0;            // inv = n0^-1 mod 2^32 by Newton iteration
   for (int i = 0; i < 5; ++i) inv *= 2u - n0 * inv;
-  *n0inv = (0u - inv) & MASK28;
+  *n0inv = (0u - inv) & ((1u << W) - 1);
   int top = nwords - 1;
   while (top > 0 && n[top] == 0) --top;
   int bits = 32 * top + 32;
@@ -150,7 +152,7 @@ inline bool mont_setup(const uint8_t* n_be, uint32_t n_len, int nlimbs, uint32_t
   const int k = (bits + 64) / 64;                                    // host domain R' = 2^(64k) just above n: n < 2^(64k - 1)
   if (bits == 1) { for (int j = 0; j < nlimbs; ++j) r2_limbs[j] = 0; return true; }      // n == 1: everything is 0
   // a modulus outside the contract (no caller passes one: they check the width first) gets whatever the defining form gives it
-  if (bits > 28 * nlimbs - 2) return mont_setup_by_doubling(n_be, n_len, nlimbs, n_limbs, r2_limbs, n0inv);
+  if (bits > W * nlimbs - 2) return mont_setup_by_doubling(n_be, n_len, nlimbs, n_limbs, r2_limbs, n0inv, W);
   std::vector<uint64_t> m(k, 0), acc(k, 0), one(k, 0);
   for (int i = 0; i < nwords && i < 2 * k; ++i) m[i >> 1] |= (uint64_t)n[i] << (32 * (i & 1));
   uint64_t m0inv = m[0];                                             // m0^-1 mod 2^64
@@ -159,7 +161,7 @@ inline bool mont_setup(const uint8_t* n_be, uint32_t n_len, int nlimbs, uint32_t
   acc[(bits - 1) >> 6] = 1ull << ((bits - 1) & 63);                  // 2^(bits-1) < n
   for (int i = bits - 1; i < 64 * k; ++i) dbl_mod64(acc.data(), m.data(), k);     // R' mod n
   dbl_mod64(acc.data(), m.data(), k);                                // 2 in the host domain
-  const uint32_t e = 2u * 28u * (uint32_t)nlimbs;
+  const uint32_t e = 2u * (uint32_t)W * (uint32_t)nlimbs;
   int hb = 31;
   while (!((e >> hb) & 1u)) --hb;
   for (int b = hb - 1; b >= 0; --b) {
@@ -170,7 +172,7 @@ inline bool mont_setup(const uint8_t* n_be, uint32_t n_len, int nlimbs, uint32_t
   montmul64(acc.data(), one.data(), m.data(), m0inv, k, acc.data());  // out of the host domain: 2^e mod n
   std::vector<uint32_t> r(nwords, 0);
   for (int i = 0; i < nwords && i < 2 * k; ++i) r[i] = (uint32_t)(acc[i >> 1] >> (32 * (i & 1)));
-  to_limbs28(r.data(), nwords, r2_limbs, nlimbs);
+  to_limbs(r.data(), nwords, r2_limbs, nlimbs, W);
   return true;
 }
 

@@ -10,8 +10,8 @@
 //                         (the reference re-hashes the whole payload per signature,
 //                          crypto/pgp/crypto_pgp.go:490); k_hash_mid_other: SHA-1/224/384/512 on demand
 //   k_digest_sha256/other per signature: finish the hash with the hash suffix, hash-tag check
-//   k_rsa_modexp<L,TPI>   s^e mod n by Montgomery ladder, 4 (8) lanes per signature (mont28.h), EMSA padding above the
-//                         low 84 bytes checked in place; runs CONCURRENTLY with the hash kernels (separate HIP stream)
+//   k_rsa_modexp<L,TPI,W> s^e mod n by Montgomery ladder, 4 (8) lanes per signature, limbs of W bits (mont28.h), EMSA padding
+//                         above the low 84 bytes checked in place; runs CONCURRENTLY with the hash kernels (separate HIP stream)
 //   k_rsa_compare         low 84 bytes of EMSA-PKCS1-v1_5 from the digest against those of s^e mod n
 //   k_dsa_inv/_mul/_modexp  dsa.Verify: s^-1 mod q and u2 on a third stream, u1 after the digests, g^u1 y^u2 mod p
 //                         from HBM-resident fixed-base window tables (k_dsa_build_comb), v mod q == r in place
@@ -206,6 +206,11 @@ __host__ __device__ __forceinline__ bool parse_sig_body(B body, uint32_t blen, S
 // creation time, 8-octet issuer key id, public-key and hash algorithm, 16-bit hash tag, MPIs.  The hashed material is the
 // 5 bytes type || creation time (body[2..7)) with NO trailer -- rec.hashed_len stays 0 and SIGF_V3 tells the digest kernels.
 constexpr uint8_t SIGF_LONG_VALUE = 1, SIGF_V3 = 2, SIGF_MORE_CANDIDATES = 4, SIGF_TEXT = 8;   // MORE: other keys share the issuer id (k_candidates)
+// RSA value under a <= 2048-bit key too long for the 72 limbs of 29 bits of k_rsa_modexp<18,4,29> (262 .. 266 bytes): the 76-limb
+// form takes it (pk_count[5] says that a call holds one)
+constexpr uint8_t SIGF_WIDE_VALUE = 16;
+constexpr int RSA29_W = 29, RSA29_L = 18, RSA29_N = RSA29_L * MONT_TPI;     // 72 limbs: R = 2^2088
+constexpr uint32_t RSA29_CAP_BYTES = RSA29_N * RSA29_W / 8;               // 261
 template <class B = const uint8_t*>
 __host__ __device__ __forceinline__ bool parse_sig_body_v3(B body, uint32_t blen, SigRec& rec, uint64_t& issuer) {
   if (blen < 1 || body[0] < 2 || body[0] > 3) return false;      // "signature packet version"
@@ -613,7 +618,8 @@ struct ParseArgs {
   const uint8_t* sig_blob; const uint64_t* sig_off; const uint32_t* rec_base; const uint32_t* counts; uint32_t n_items;
   const WalkEnt* scratch; uint32_t walk_cap; SigRec* recs; uint32_t n_recs; const uint32_t* cert_ent;
   uint32_t *pk_list, *pk_list3072, *pk_list4096;
-  uint32_t* pk_count;          // [0] RSA<=2048, [1] DSA, [2] RSA<=3072, [3] RSA<=4096, [4] some hash other than SHA-256
+  uint32_t* pk_count;          // [0] RSA<=2048, [1] DSA, [2] RSA<=3072, [3] RSA<=4096, [4] some hash other than SHA-256,
+                               // [5] some RSA value under a <= 2048-bit key is longer than 261 bytes (SIGF_WIDE_VALUE)
   uint32_t* dsa_list; uint32_t* item_hash_mask;
   const uint8_t* sig_class;    // per item or null
   // per item or null, certificate checks only (sig_class >= 1): the id of the key the CALLER holds for this check -- x/crypto's
@@ -793,6 +799,7 @@ __device__ __forceinline__ void parse_one(const ParseArgs& a, const KeyTableDev&
           else {
             rec.after_tag = AFTER_TAG_PUBKEY;
             rec.flags |= (vbytes > kbytes) ? SIGF_LONG_VALUE : 0;
+            if (cls_sz == 0 && vbytes > RSA29_CAP_BYTES) { rec.flags |= SIGF_WIDE_VALUE; pk_count[5] = 1u; }
             q_kind = cls_sz == 0 ? 0 : (int)cls_sz + 1;                         // [0] <=2048, [1] DSA, [2] <=3072, [3] <=4096
           }
         } else if (rec.pk_algo == PK_DSA) {
@@ -1139,15 +1146,15 @@ __device__ __forceinline__ uint32_t tail_byte(const TailSrc& t, uint32_t j) {
   return (t.pre_len >> (8 * (5 - j))) & 0xFF;
 }
 
-// value of a big-endian byte string as radix-2^28 limb j
-template <typename F>
-__device__ __forceinline__ uint32_t limb28(F byte_from_lsb, int j) {
-  uint32_t bit = 28u * (uint32_t)j;
+// value of a big-endian byte string as radix-2^W limb j (W + 7 <= 40: five bytes hold any limb)
+template <int W = MONT_W, typename F>
+__device__ __forceinline__ uint32_t limb_of(F byte_from_lsb, int j) {
+  uint32_t bit = (uint32_t)W * (uint32_t)j;
   uint32_t b0 = bit >> 3, sh = bit & 7;
   uint64_t v = 0;
 #pragma unroll
   for (int t = 0; t < 5; ++t) v |= (uint64_t)byte_from_lsb(b0 + t) << (8 * t);
-  return (uint32_t)(v >> sh) & MONT_MASK;
+  return (uint32_t)(v >> sh) & ((1u << W) - 1);
 }
 
 // Per signature: digest = H(signed || hash suffix) from the item's midstate; hash-tag check.
@@ -1340,6 +1347,12 @@ constexpr int QUADS_PER_BLOCK = RSA_BLOCK / MONT_TPI;
 #define BFTKV_MODEXP_BLOCK 256
 #endif
 constexpr int MODEXP_BLOCK = BFTKV_MODEXP_BLOCK;
+// The 4-lane form of k_rsa_modexp for big calls: 29 = 18 x 4 limbs of 29 bits (147,456 limb products per e = 65537 verify),
+// 28 = 19 x 4 limbs of 28 bits (164,160), the form before it -- kept so that the two can be measured as two builds of one tree.
+#ifndef BFTKV_RSA_FORM
+#define BFTKV_RSA_FORM 29
+#endif
+static_assert(BFTKV_RSA_FORM == 28 || BFTKV_RSA_FORM == 29, "BFTKV_RSA_FORM: 28 or 29");
 
 enum : int { OP_TO_MONT = 0, OP_SQR = 1, OP_MULX = 2, OP_MULP = 3, OP_MUL1 = 4 };
 
@@ -1352,23 +1365,32 @@ constexpr int EM_LOW_LIMBS = EM_LOW_BYTES * 8 / MONT_W;     // 24: 84 bytes are 
 static_assert(EM_LOW_LIMBS * MONT_W == EM_LOW_BYTES * 8, "the EM split must fall on a limb boundary");
 constexpr uint32_t EM_HEAD_BAD = 0xFFFFFFFFu;               // no canonical limb: marks a residue whose upper part is not padding
 
-// Limb gi (>= EM_LOW_LIMBS) of 00 01 FF .. FF for a modulus of kbytes bytes: ones from bit 8*EM_LOW_BYTES up to and
-// including bit 8*(kbytes-2), the 01 byte.
+// Radix-2^W limb gi of 00 01 FF .. FF for a modulus of kbytes bytes: ones up to and including bit 8*(kbytes-2), the 01
+// byte.  Meant for the limbs above bit 8*EM_LOW_BYTES; of a limb that straddles that bit (W = 29: limb 23) the caller
+// compares the upper part only.
+template <int W = MONT_W>
 __device__ __forceinline__ uint32_t em_head_limb(uint32_t gi, uint32_t kbytes) {
-  const int32_t top = 8 * ((int32_t)kbytes - 2), lo = (int32_t)gi * MONT_W;
+  const int32_t top = 8 * ((int32_t)kbytes - 2), lo = (int32_t)gi * W;
   if (top < lo) return 0u;
-  if (top >= lo + MONT_W - 1) return MONT_MASK;
+  if (top >= lo + W - 1) return (1u << W) - 1u;
   return (1u << (top - lo + 1)) - 1u;
 }
 
 // r = s^e mod n for every queued signature: the upper limbs checked against the EMSA padding here, the low EM_LOW_LIMBS
-// limbs (canonical radix 2^28) to r_low for k_rsa_compare.
-template <int L, int TPI>   // limbs per lane x lanes per number: 19x4 (<= 2048-bit moduli), 14x8 (<= 3072), 19x8 (<= 4096)
+// limbs (canonical radix 2^28, whatever the kernel's own radix) to r_low for k_rsa_compare.
+//   wide_word: a device word that says whether the list holds values of 262 .. 266 bytes under a <= 2048-bit key
+//   (SIGF_WIDE_VALUE, k_parse_body).  The 29-bit form leaves those groups alone; the 28-bit form launched right behind it as
+//   WIDE_ONLY takes only them, and its blocks return at once when the word is zero.  Every other form ignores it.
+// limbs per lane x lanes per number x limb width: 18x4 at 2^29 (<= 2048-bit moduli), 19x4 (the same class: values too long
+// for 72 limbs, and -DBFTKV_RSA_FORM=28), 10x8 (small calls), 14x8 (<= 3072), 19x8 (<= 4096)
+template <int L, int TPI, int W = MONT_W, bool WIDE_ONLY = false>
 __global__ void __launch_bounds__(MODEXP_BLOCK, 3) k_rsa_modexp(const uint8_t* __restrict__ sig_blob, const SigRec* __restrict__ recs,
                                                           const uint32_t* __restrict__ pk_list, const uint32_t* __restrict__ pk_count_ptr,
                                                           const uint32_t* __restrict__ pk_start_ptr,
                                                           KeyTableDev kt, uint32_t* __restrict__ r_low,
-                                                          uint32_t* __restrict__ xr_scratch, uint64_t* __restrict__ clk) {
+                                                          uint32_t* __restrict__ xr_scratch, uint64_t* __restrict__ clk,
+                                                          const uint32_t* __restrict__ wide_word = nullptr) {
+  static_assert(W == MONT_W || (W == 29 && L == 18 && TPI == 4 && !WIDE_ONLY), "the only form at another radix is 18 x 4 at 2^29");
   constexpr int NL = TPI * L;
   constexpr int GROUPS = MODEXP_BLOCK / TPI;   // numbers per block
   // diagnostics: shader-clock ticks (s_memtime) and constant 100 MHz ticks (s_memrealtime) over the life of block 0's first
@@ -1381,10 +1403,17 @@ __global__ void __launch_bounds__(MODEXP_BLOCK, 3) k_rsa_modexp(const uint8_t* _
   // work = list entries [start, count): phase 1 of a call starts at 0, phase 2 where phase 1 ended (k_plan)
   const uint32_t count = *pk_count_ptr, start = *pk_start_ptr;
   if (start + blockIdx.x * GROUPS >= count) return;   // whole block idle
+  if constexpr (WIDE_ONLY) { if (*wide_word == 0u) return; }   // the pass for values too long for the 29-bit form: there are none
   const uint32_t quad = threadIdx.x / TPI;
   const int qlane = threadIdx.x % TPI;
   const uint32_t gq = start + blockIdx.x * GROUPS + quad;
-  const bool active = gq < count;
+  bool active = gq < count;
+  if constexpr (W != MONT_W || WIDE_ONLY) {
+    // this pass's share of the list; a group of the other pass's goes through the motions as padding does
+    const bool wide = active && (recs[pk_list[gq]].flags & SIGF_WIDE_VALUE) != 0;
+    active = active && (wide == WIDE_ONLY);
+    if (WIDE_ONLY && !__any(active)) return;          // (waves never meet: one without work of this pass leaves)
+  }
   const uint32_t pi = active ? gq : (count - 1);
   const uint32_t ri = pk_list[pi];
   const SigRec rec = recs[ri];
@@ -1394,27 +1423,29 @@ __global__ void __launch_bounds__(MODEXP_BLOCK, 3) k_rsa_modexp(const uint8_t* _
   uint32_t* x_lds = x_sh + quad * NL + qlane * L;
 
   uint32_t n[L], b[L], y[L];
-  const uint32_t* np = kt.n_limbs + (uint64_t)key * MONT_NMAX + qlane * L;
+  const uint32_t* np = W == 29 ? kt.n_limbs29 + (uint64_t)key * NL + qlane * L : kt.n_limbs + (uint64_t)key * MONT_NMAX + qlane * L;
   // <10, 8>: a <= 2048-bit modulus over eight lanes (80 limbs, R = 2^2240) -- 0.68x the instructions of <19, 4> per wave, the
   // shorter chain for calls too small to fill the machine either way (run_pipeline picks it below ~8k signatures)
-  const uint32_t* rp = (L == 10 && TPI == 8) ? kt.r2_limbs80 + (uint64_t)key * 80 + qlane * L
-                                              : kt.r2_limbs + (uint64_t)key * MONT_NMAX + qlane * L;
+  const uint32_t* rp = W == 29                 ? kt.r2_limbs29 + (uint64_t)key * NL + qlane * L      // (2^2088)^2 mod n
+                       : (L == 10 && TPI == 8) ? kt.r2_limbs80 + (uint64_t)key * 80 + qlane * L
+                                               : kt.r2_limbs + (uint64_t)key * MONT_NMAX + qlane * L;
   uint32_t* xrp = xr_scratch + (uint64_t)pi * NL + qlane * L;
 #pragma unroll
   for (int k = 0; k < L; ++k) n[k] = np[k];
-  // signature value: big-endian MPI bytes -> this lane's 19 limbs
+  // signature value: big-endian MPI bytes -> this lane's L limbs
   {
     const uint32_t nb = (rec.mpi_bits[0] + 7u) >> 3;
     const uint8_t* mp = sig_blob + rec.body_off + rec.mpi_off[0];
     auto sig_b = [&](uint32_t i) -> uint32_t { return i < nb ? mp[nb - 1 - i] : 0u; };
 #pragma unroll
-    for (int k = 0; k < L; ++k) x_lds[k] = limb28(sig_b, qlane * L + k);
+    for (int k = 0; k < L; ++k) x_lds[k] = limb_of<W>(sig_b, qlane * L + k);
   }
-  const uint32_t n0inv = kt.n0inv[key];
+  const uint32_t n0inv = W == 29 ? kt.n0inv29[key] : kt.n0inv[key];
   const uint32_t e = kt.rsa_e[key];
   const uint32_t kbytes = (kt.mod_bits[key] + 7) >> 3;
   // x-shortcut: the last multiplication of an odd exponent uses plain x instead of xR, which also
-  // leaves the Montgomery domain.  Only when x < 2^(8k) so that the result stays below n(1+2^-79).
+  // leaves the Montgomery domain.  Only when x < 2^(8k) so that the result stays below n(1+2^-79) (18 x 4 at 2^29,
+  // R = 2^2088: n(1+2^-39)).
   const uint32_t cls = (e << 1) | (((e & 1u) && e > 1u && !(rec.flags & 1u)) ? 1u : 0u);
 
   // Exponent schedules are wave-uniform per (e, shortcut) class; a wave whose 16 signatures use
@@ -1452,8 +1483,8 @@ __global__ void __launch_bounds__(MODEXP_BLOCK, 3) k_rsa_modexp(const uint8_t* _
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       // 16 of the 18 products of e = 65537 are squarings: half the a*b limb products (mont28.h, SQR)
-      if (kind == OP_SQR) mont_mul<L, TPI, true>(y, a_rd, b, n, n0inv, qlane);
-      else mont_mul<L, TPI, false>(y, a_rd, b, n, n0inv, qlane);
+      if (kind == OP_SQR) mont_mul<L, TPI, true, W>(y, a_rd, b, n, n0inv, qlane);
+      else mont_mul<L, TPI, false, W>(y, a_rd, b, n, n0inv, qlane);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       // ---- next step (scalar control flow)
       if (kind == OP_TO_MONT && (e_u & (e_u - 1u)) != 0 && !(sc_u && __builtin_popcount(e_u) == 2)) {
@@ -1469,29 +1500,55 @@ __global__ void __launch_bounds__(MODEXP_BLOCK, 3) k_rsa_modexp(const uint8_t* _
     // or by the plain value x < 2^(8k) (y < n(1 + 2^(8k+1)/R), R = 2^2128 / 2^3136 / 2^4256).  An encoded message is at
     // least 2^(8k-16) > n * 2^-16, so such a t is no valid signature and neither is y >= n: comparing y itself with the
     // encoding gives the verdict of comparing t, without a final subtraction.
-    canonicalize<L, TPI>(y, qlane);
+    // 18 x 4 at 2^29: R = 2^2088 and x < 2^(8k) <= 2^2048 give y < n(1 + 2^-39), so y = t + n only when t < n * 2^-39, still
+    // 23 bits below the smallest encoding.
+    canonicalize<L, TPI, W>(y, qlane);
     if (e_u == 0) {                            // x^0 = 1
 #pragma unroll
       for (int k = 0; k < L; ++k) y[k] = (qlane == 0 && k == 0) ? 1u : 0u;
     }
     uint32_t head = 0;
+    if constexpr (W == MONT_W) {
 #pragma unroll
-    for (int k = 0; k < L; ++k) {
-      const uint32_t gi = (uint32_t)qlane * L + k;
-      if (gi >= (uint32_t)EM_LOW_LIMBS) head |= y[k] ^ em_head_limb(gi, kbytes);
+      for (int k = 0; k < L; ++k) {
+        const uint32_t gi = (uint32_t)qlane * L + k;
+        if (gi >= (uint32_t)EM_LOW_LIMBS) head |= y[k] ^ em_head_limb(gi, kbytes);
+      }
+    } else {
+      // the split at bit 8*EM_LOW_BYTES = 672 is no limb boundary at this radix: the limb that straddles it (23: bits
+      // 667 .. 695) is checked from bit 672 up, its low 5 bits belong to k_rsa_compare's part
+#pragma unroll
+      for (int k = 0; k < L; ++k) {
+        const int32_t lo = ((int32_t)qlane * L + k) * W, cut = 8 * EM_LOW_BYTES;
+        if (lo + W > cut) {
+          const uint32_t d = y[k] ^ em_head_limb<W>((uint32_t)qlane * L + k, kbytes);
+          head |= (lo < cut) ? d >> (cut - lo) : d;
+        }
+      }
     }
     head = grp_or<TPI>(head);
     // the low limbs leave through the group's LDS slice (free now): each of the group's first four lanes stores six
     // consecutive limbs, so a wave writes one contiguous run
-    if (head != 0 && qlane == 0) y[0] = EM_HEAD_BAD;
+    if (W == MONT_W && head != 0 && qlane == 0) y[0] = EM_HEAD_BAD;
 #pragma unroll
     for (int k = 0; k < L; ++k) a_lds[k] = y[k];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (live && active && qlane < 4) {
       uint32_t* out = r_low + (uint64_t)pi * EM_LOW_LIMBS + qlane * (EM_LOW_LIMBS / 4);
-      const uint32_t* src = a_rd + qlane * (EM_LOW_LIMBS / 4);
+      if constexpr (W == MONT_W) {
+        const uint32_t* src = a_rd + qlane * (EM_LOW_LIMBS / 4);
 #pragma unroll
-      for (int k = 0; k < EM_LOW_LIMBS / 4; ++k) out[k] = src[k];
+        for (int k = 0; k < EM_LOW_LIMBS / 4; ++k) out[k] = src[k];
+      } else {
+        // re-cut the low 672 bits into 28-bit limbs: limb j of the output starts at bit 28 j, inside limb 28 j / W here, and
+        // ends in that limb or the next (the last one, 23, ends with the low 5 bits of limb 23)
+#pragma unroll
+        for (int k = 0; k < EM_LOW_LIMBS / 4; ++k) {
+          const uint32_t bit = (uint32_t)MONT_W * ((uint32_t)qlane * (EM_LOW_LIMBS / 4) + k), i = bit / W, sh = bit % W;
+          const uint32_t v = ((a_rd[i] >> sh) | (a_rd[i + 1] << (W - sh))) & MONT_MASK;
+          out[k] = (head != 0 && qlane == 0 && k == 0) ? EM_HEAD_BAD : v;
+        }
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     todo &= ~__builtin_amdgcn_ballot_w64(live);
@@ -2160,7 +2217,7 @@ __global__ void k_bytes_to_limbs(const uint8_t* __restrict__ src, uint32_t nbyte
   uint32_t num = i / MONT_N, j = i % MONT_N;
   const uint8_t* p = src + (uint64_t)num * nbytes;
   auto bf = [&](uint32_t k) -> uint32_t { return k < nbytes ? p[nbytes - 1 - k] : 0u; };
-  dst[i] = limb28(bf, (int)j);
+  dst[i] = limb_of(bf, (int)j);
 }
 __global__ void k_limbs_to_bytes(const uint32_t* __restrict__ src, uint32_t nbytes, uint32_t n_nums, uint8_t* __restrict__ dst) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

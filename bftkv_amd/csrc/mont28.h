@@ -3,7 +3,8 @@
 // Design:
 //   * radix 2^28 limbs, L limbs per lane, TPI lanes per number: 19 x 4 (<= 2048-bit moduli, R = 2^2128), 14 x 8 (<= 3072,
 //     R = 2^3136), 19 x 8 (<= 4096, R = 2^4256), 10 x 8 (k_multiexp's form for small calls, R = 2^2240); R > 4n, so values
-//     stay < 2n with NO conditional subtraction between multiplications;
+//     stay < 2n with NO conditional subtraction between multiplications.  The limb width is a template parameter (default
+//     MONT_W): k_rsa_modexp's <= 2048-bit form is 18 x 4 at radix 2^29 (R = 2^2088 > 4n), 10 % fewer limb products;
 //   * lazy carries: every limb product is ONE v_mad_u64_u32 into a 64-bit column accumulator (152 products of < 2^56.6 fit
 //     in 64 bits).  Measured on MI355X (tools/microbench): a wave64 v_mad_u64_u32 holds a SIMD's issue port for 4.64 cycles,
 //     a 64-bit add or shift for ~4.3, a plain 32-bit op for 2.3 -- the multiplier is barely dearer than a carry, so the loop
@@ -96,14 +97,14 @@ __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c) {
 //   before the first block it is 0.
 // Group lane TPI-1 reads the next group's lane 0, whose retired columns are zero by construction; the last lane of a DPP
 // row reads 0 through bound_ctrl.
-template <int L, int TPI, bool SQR, int O>
+template <int L, int TPI, bool SQR, int O, int W = MONT_W>
 __device__ __forceinline__ void mont_block_ring(uint64_t (&Q)[2 * L], const uint32_t* ap, const uint32_t (&b)[L],
                                                 const uint32_t (&n)[L], uint32_t n0inv, int qlane, uint32_t mask_v) {
   constexpr int M = 2 * L;
 #pragma unroll
   for (int r = 0; r < L; ++r) {
     const uint32_t ai = ap[r];
-    const uint32_t ai2 = ai << 1;      // SQR: off-diagonal products count twice (limbs <= 2^28: the product stays < 2^57)
+    const uint32_t ai2 = ai << 1;      // SQR: off-diagonal products count twice (limbs <= 2^W: the product stays < 2^(2W+1))
     uint64_t in = 0;
     if (r > 0) in = dpp_row_shl1((uint32_t)Q[(O + r - 1) % M]) & mask_v;   // v_and_b32_dpp; the high half stays 0
     // Q[r+k] += a_i * b[k]
@@ -119,7 +120,7 @@ __device__ __forceinline__ void mont_block_ring(uint64_t (&Q)[2 * L], const uint
     for (int k = 0; k < L; ++k) Q[(O + r + k) % M] = mad64(m, n[k], Q[(O + r + k) % M]);
     // retire column r: push its carry into column r+1.  What stays behind is the column's low 28 bits (zero in group
     // lane 0 by construction); the mask is applied where the previous lane reads them, in its next row.
-    Q[(O + r + 1) % M] += Q[(O + r) % M] >> MONT_W;
+    Q[(O + r + 1) % M] += Q[(O + r) % M] >> W;
   }
   // the limb retired by the last row: column L-1 of the next block (the addend of its row 0, k = L-1 MAC), or the top
   // limb of the result
@@ -142,7 +143,7 @@ __device__ __forceinline__ void mont_block_ring(uint64_t (&Q)[2 * L], const uint
 // Every lane executes the same triangle in every step -- no idle lanes, no operand movement -- and the column order the
 // Montgomery rows rely on is unchanged (row r only touches columns >= 2r of its block).  190 instead of 361 limb products
 // per block step: 2204 instead of 2888 MACs per lane and product.
-template <int L, int TPI = MONT_TPI, bool SQR = false>
+template <int L, int TPI = MONT_TPI, bool SQR = false, int W = MONT_W>
 __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_lds,
                                          const uint32_t (&b)[L], const uint32_t (&n)[L],
                                          uint32_t n0inv, int qlane) {
@@ -152,10 +153,16 @@ __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_l
   // for L = 19 with every limb and every Montgomery factor at its maximum, in the ring forms and in the normalising one
   // alike -- NOT the 2N = 2*TPI*L products this comment used to count, of which 255 would fit.  The switch below still
   // follows that older count: the 152-limb form carry-normalises its live columns at every block boundary.
+  // The 18 x 4 form at radix 2^29 (W = 29, <= 2048-bit moduli, R = 2^2088): 36 products of at most 2^58 per column plus a
+  // carry, 0.5625 * 2^64 with every limb of a at 2^29, every limb of n and every Montgomery factor at 2^29 - 1, squaring and
+  // general form alike (tests/test_mont29_model.py) -- it runs on the ring with no normalisation.
   constexpr bool NORM = 2 * TPI * L > 255;
   static_assert(TPI % 2 == 0, "the ring window runs two blocks per loop iteration");
+  static_assert(W == 28 || (W == 29 && !NORM && L <= 18), "a 29-bit limb fits the column only in a ring form of at most 18 rows per block");
+  constexpr uint32_t MASK = (1u << W) - 1;
   uint32_t mask_v;   // the limb mask in a VGPR: lets the Montgomery factor's mask carry the quad broadcast (v_and_b32_dpp)
-  asm("v_mov_b32 %0, 0xfffffff" : "=v"(mask_v));
+  if constexpr (W == 28) asm("v_mov_b32 %0, 0xfffffff" : "=v"(mask_v));
+  else asm("v_mov_b32 %0, 0x1fffffff" : "=v"(mask_v));
   uint64_t Q[NORM ? 2 * L - 1 : 2 * L];   // the ring, or (NORM) a window of 2L-1 columns
 #pragma unroll
   for (int k = 0; k < L + (NORM ? 1 : 0); ++k) Q[k] = 0;
@@ -164,8 +171,8 @@ __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_l
     // TPI is even, so the last block runs at offset L and leaves the result in Q[0 .. L-1]
 #pragma unroll 1
     for (int blk = 0; blk < TPI; blk += 2) {
-      mont_block_ring<L, TPI, SQR, 0>(Q, a_lds + blk * L, b, n, n0inv, qlane, mask_v);
-      mont_block_ring<L, TPI, SQR, L>(Q, a_lds + (blk + 1) * L, b, n, n0inv, qlane, mask_v);
+      mont_block_ring<L, TPI, SQR, 0, W>(Q, a_lds + blk * L, b, n, n0inv, qlane, mask_v);
+      mont_block_ring<L, TPI, SQR, L, W>(Q, a_lds + (blk + 1) * L, b, n, n0inv, qlane, mask_v);
     }
   } else {
 #pragma unroll 1
@@ -185,7 +192,7 @@ __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_l
         const uint32_t m = grp_bcast0<TPI>((uint32_t)Q[r] * n0inv, qlane) & mask_v;
 #pragma unroll
         for (int k = 0; k < L; ++k) Q[r + k] = mad64(m, n[k], Q[r + k]);
-        Q[r + 1] += Q[r] >> MONT_W;
+        Q[r + 1] += Q[r] >> W;
       }
       // window slid by L columns = one lane: re-align.  new Q[k] = own Q[L+k] + next lane's Q[k]
 #pragma unroll
@@ -196,8 +203,8 @@ __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_l
       // carry-normalise the live columns; the top carry seeds column L (accumulated by the next first touch)
 #pragma unroll
       for (int k = 0; k < L; ++k) {
-        const uint64_t c = Q[k] >> MONT_W;
-        Q[k] &= MONT_MASK;
+        const uint64_t c = Q[k] >> W;
+        Q[k] &= MASK;
         if (k < L - 1) Q[k + 1] += c; else Q[L] = c;
       }
     }
@@ -208,23 +215,23 @@ __device__ __forceinline__ void mont_mul(uint32_t (&out)[L], const uint32_t* a_l
 #pragma unroll
   for (int k = 0; k < L; ++k) {
     uint64_t v = Q[k] + c;
-    out[k] = (uint32_t)v & MONT_MASK;
-    c = v >> MONT_W;
+    out[k] = (uint32_t)v & MASK;
+    c = v >> W;
   }
   if (NORM) c += Q[L];   // the top carry of the last block boundary belongs to the next lane's column 0
   uint32_t clo = grp_shr1<TPI>((uint32_t)c), chi = grp_shr1<TPI>((uint32_t)(c >> 32));
   uint64_t cin = (qlane == 0) ? 0 : (((uint64_t)chi << 32) | clo);
   uint64_t v0 = (uint64_t)out[0] + cin;
-  out[0] = (uint32_t)v0 & MONT_MASK;
-  uint32_t v1 = out[1] + (uint32_t)(v0 >> MONT_W);
-  out[1] = v1 & MONT_MASK;
-  out[2] += v1 >> MONT_W;
+  out[0] = (uint32_t)v0 & MASK;
+  uint32_t v1 = out[1] + (uint32_t)(v0 >> W);
+  out[1] = v1 & MASK;
+  out[2] += v1 >> W;
 }
 
 // Exact canonical form (every limb < 2^28) of a lazily-normal number (limbs <= 2^28 + small).
 // Step s lets a carry hop from quad lane s-1 to lane s; lane l generates no new carry after
 // step l, so TPI steps suffice.
-template <int L, int TPI = MONT_TPI>
+template <int L, int TPI = MONT_TPI, int W = MONT_W>
 __device__ __forceinline__ void canonicalize(uint32_t (&x)[L], int qlane) {
   uint32_t cout = 0;
 #pragma unroll
@@ -234,8 +241,8 @@ __device__ __forceinline__ void canonicalize(uint32_t (&x)[L], int qlane) {
 #pragma unroll
     for (int k = 0; k < L; ++k) {
       uint32_t v = x[k] + c;
-      x[k] = v & MONT_MASK;
-      c = v >> MONT_W;
+      x[k] = v & ((1u << W) - 1);
+      c = v >> W;
     }
     cout = c;
   }
@@ -245,7 +252,7 @@ __device__ __forceinline__ void canonicalize(uint32_t (&x)[L], int qlane) {
 // The top lane of the group compares its limbs first; only a wave holding a candidate (the top limbs of y not below those
 // of n: about 2^-50 per number for a 2048-bit modulus) runs the subtraction, whose borrow hops lane to lane like
 // canonicalize's carry.
-template <int L, int TPI = MONT_TPI>
+template <int L, int TPI = MONT_TPI, int W = MONT_W>
 __device__ __forceinline__ void reduce_once(uint32_t (&y)[L], const uint32_t (&n)[L], int qlane) {
   uint32_t ge = 1;
 #pragma unroll
@@ -262,8 +269,8 @@ __device__ __forceinline__ void reduce_once(uint32_t (&y)[L], const uint32_t (&n
 #pragma unroll
     for (int k = 0; k < L; ++k) {
       const int32_t v = (int32_t)d[k] + c;
-      d[k] = (uint32_t)v & MONT_MASK;
-      c = v >> MONT_W;                                        // arithmetic shift: -1 = borrow
+      d[k] = (uint32_t)v & ((1u << W) - 1);
+      c = v >> W;                                             // arithmetic shift: -1 = borrow
     }
     cout = c;
     top += c;                                                 // borrows that left this lane, over all steps

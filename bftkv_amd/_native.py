@@ -52,6 +52,8 @@ EXPORTS = [
     "bftkv_gpu_dsa_verify", "bftkv_gpu_dsa_verify_dev", "bftkv_gpu_batcher_dsa_verify",
     "bftkv_gpu_ecdsa_keyset_create", "bftkv_gpu_ecdsa_keyset_destroy", "bftkv_gpu_ecdsa_keyset_info", "bftkv_gpu_ecdsa_verify_keyset",
     "bftkv_gpu_ecdsa_verify_keyset_dev", "bftkv_gpu_batcher_ecdsa_verify_keyset", "bftkv_gpu_selftest_ecdsa_keyset_table",
+    "bftkv_gpu_dsa_keyset_create", "bftkv_gpu_dsa_keyset_destroy", "bftkv_gpu_dsa_keyset_info", "bftkv_gpu_dsa_verify_keyset",
+    "bftkv_gpu_dsa_verify_keyset_dev", "bftkv_gpu_batcher_dsa_verify_keyset", "bftkv_gpu_selftest_dsa_keyset_table",
 ]
 
 _lib = None
@@ -155,6 +157,13 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_ecdsa_verify_keyset_dev.argtypes = lib.bftkv_gpu_ecdsa_verify_keyset.argtypes
     lib.bftkv_gpu_batcher_ecdsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, u8p, u8p]
     lib.bftkv_gpu_selftest_ecdsa_keyset_table.argtypes = [vp, C.c_int, u32, vp, C.c_uint64]
+    lib.bftkv_gpu_dsa_keyset_create.argtypes = [vp, u32, u8p, vp, u32, u32, u8p, u8p, u8p, u32, u32, C.POINTER(C.c_int)]
+    lib.bftkv_gpu_dsa_keyset_destroy.argtypes = [vp, C.c_int]
+    lib.bftkv_gpu_dsa_keyset_info.argtypes = [vp, C.c_int] + [C.POINTER(u32)] * 6 + [C.POINTER(C.c_uint64)]
+    lib.bftkv_gpu_dsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, vp, u8p, u8p]
+    lib.bftkv_gpu_dsa_verify_keyset_dev.argtypes = lib.bftkv_gpu_dsa_verify_keyset.argtypes
+    lib.bftkv_gpu_batcher_dsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, u8p, u8p]
+    lib.bftkv_gpu_selftest_dsa_keyset_table.argtypes = [vp, C.c_int, u32, vp, C.c_uint64]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -692,6 +701,56 @@ class Context:
         self._check(self.lib.bftkv_gpu_selftest_ecdsa_keyset_table(self.h, keyset, key, words.ctypes.data, len(words)), "selftest_ecdsa_keyset_table")
         return words
 
+    def dsa_keyset_create(self, keys, groups, window_bits=0, pbytes=None, qbytes=None) -> int:
+        """Register groups [(p, q, g)] ints and keys [(group, y)] once: the Montgomery rows and a fixed-base window table per g and
+        y on the device.  window_bits 4 .. 16, 0 for the default of 8; pbytes / qbytes default to the width of the widest p, g, y
+        and of the widest q."""
+        if qbytes is None:
+            qbytes = max(1, max((int(g[1]).bit_length() + 7) // 8 for g in groups))
+        if pbytes is None:
+            pbytes = max(1, max((int(v).bit_length() + 7) // 8 for v in [g[0] for g in groups] + [g[2] for g in groups] + [k[1] for k in keys]))
+        p, q, g = (_ints_to_be([grp[i] for grp in groups], w) for i, w in ((0, pbytes), (1, qbytes), (2, pbytes)))
+        y = _ints_to_be([k[1] for k in keys], pbytes)
+        kg = np.ascontiguousarray([k[0] for k in keys], dtype=np.uint32)
+        h = C.c_int(-1)
+        self._check(self.lib.bftkv_gpu_dsa_keyset_create(self.h, len(keys), _ptr(y), _ptr(kg), pbytes, len(groups), _ptr(p), _ptr(q), _ptr(g), qbytes,
+                                                         window_bits, C.byref(h)), "dsa_keyset_create")
+        return h.value
+
+    def dsa_keyset_destroy(self, keyset: int):
+        self._check(self.lib.bftkv_gpu_dsa_keyset_destroy(self.h, keyset), "dsa_keyset_destroy")
+
+    def dsa_keyset_info(self, keyset: int):
+        """-> {n_keys, n_groups, pbytes, qbytes, window_bits, windows, table_bytes}"""
+        v = [C.c_uint32() for _ in range(6)]
+        tb = C.c_uint64()
+        self._check(self.lib.bftkv_gpu_dsa_keyset_info(self.h, keyset, *[C.byref(x) for x in v], C.byref(tb)), "dsa_keyset_info")
+        names = ("n_keys", "n_groups", "pbytes", "qbytes", "window_bits", "windows")
+        return dict(zip(names, (x.value for x in v)), table_bytes=tb.value)
+
+    def dsa_verify_keyset(self, keyset: int, digests, sigs, key_idx=None):
+        """dsa_verify under the keys of a set: digests [n_ops] bytes of ONE length (1..64), sigs [n_ops] bytes r || s (2 qbytes of
+        the set), key_idx [n_ops] into the set or None (key 0) -> (valid, status), uint8 each."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        slen = 2 * self.dsa_keyset_info(keyset)["qbytes"]
+        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or len(sigs) != n:
+            raise ValueError("dsa_verify_keyset: digests of one length, sigs of 2 qbytes")
+        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_dsa_verify_keyset(self.h, keyset, n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki),
+                                                         _ptr(valid), _ptr(st)), "dsa_verify_keyset")
+        return valid[:n], st[:n]
+
+    def selftest_dsa_keyset_table(self, keyset: int, base: int) -> np.ndarray:
+        """One base's table as the device built it (the groups' g first, then the keys' y): uint32 [windows][2^w - 1][76]."""
+        info = self.dsa_keyset_info(keyset)
+        nent = (1 << info["window_bits"]) - 1
+        words = np.zeros(info["windows"] * nent * 76, dtype=np.uint32)
+        self._check(self.lib.bftkv_gpu_selftest_dsa_keyset_table(self.h, keyset, base, words.ctypes.data, len(words)), "selftest_dsa_keyset_table")
+        return words.reshape(info["windows"], nent, 76)
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -840,6 +899,15 @@ class Batcher:
         dg, sg = _u8(digest), _u8(sig)
         valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
         rc = self.lib.bftkv_gpu_batcher_ecdsa_verify_keyset(self.h, keyset, key, _ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
+
+    def dsa_verify_keyset(self, keyset: int, key: int, digest: bytes, sig: bytes):
+        """crypto/dsa.Verify for one raw signature r || s under key `key` of a resident DSA key set -> (rc, status, valid)."""
+        if not digest or len(sig) != 2 * self.ctx.dsa_keyset_info(keyset)["qbytes"]:
+            raise ValueError("dsa_verify_keyset: sig of 2 qbytes of the set, a non-empty digest")
+        dg, sg = _u8(digest), _u8(sig)
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_dsa_verify_keyset(self.h, keyset, key, _ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
         return rc, int(st[0]), int(valid[0])
 
     def modexp(self, base: int, exp: int, mod: int, nbytes: int = 256, exp_len: int = 32):

@@ -310,7 +310,7 @@ struct bftkv_gpu_batcher {
     const int32_t* th_xs = nullptr;
     const uint8_t *th_a = nullptr, *th_b = nullptr, *th_mod = nullptr, *th_mod2 = nullptr;
     uint8_t* th_out = nullptr;
-    uint32_t ks_key = 0;       // kind 10: the key's index within the set
+    uint32_t ks_key = 0;       // kinds 10, 12: the key's index within the set
     const uint8_t *th_g = nullptr, *th_y = nullptr;      // kind 11: the group's generator and the public value (th_nbytes each)
   };
   struct Batch {
@@ -598,6 +598,41 @@ struct bftkv_gpu_batcher {
     }
   }
 
+  // kind 12: DSA verification under a resident key set, as kind 10: a group's callers share the set (Req::quorum) and a digest length
+  // (th_k); th_a = digest, th_b = r || s, ks_key = the key's index in the set.  The lane holds the root's tables from the look at the
+  // set's qbytes to the end of the device call, so the set cannot be replaced by one of another signature length in between.
+  void run_dsa_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k;
+    std::vector<uint8_t> valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    int rc;
+    {
+      ctx_lock lk(lane.ctx->mu);
+      KtRead kr(lane.ctx);
+      const DsaKeySet* ks = kr.rc ? nullptr : dsa_keyset_find(lane.ctx, r0.quorum);
+      if (kr.rc) rc = kr.rc;
+      else if (!ks) rc = BFTKV_E_INVALID;
+      else {
+        const uint32_t qb = ks->qbytes;
+        std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * qb);
+        std::vector<uint32_t> idx(n);
+        for (uint32_t i = 0; i < n; ++i) {
+          memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
+          memcpy(&sg[(size_t)i * 2 * qb], g[i]->th_b, 2 * (size_t)qb);
+          idx[i] = g[i]->ks_key;
+        }
+        rc = dsa_verify_keyset_impl(lane.ctx, r0.quorum, n, dg.data(), dlen, sg.data(), idx.data(), valid.data(), st.data(), false);
+        ++device_calls;
+      }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(12) : st[i];
+      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
+    }
+  }
+
   void run_threshold(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const int kind = r0.kind;
@@ -605,6 +640,7 @@ struct bftkv_gpu_batcher {
     if (kind == 8) { run_ecdsa(lane, g, device_calls); return; }
     if (kind == 9) { run_ecdsa_verify(lane, g, device_calls); return; }
     if (kind == 10) { run_ecdsa_verify_keyset(lane, g, device_calls); return; }
+    if (kind == 12) { run_dsa_verify_keyset(lane, g, device_calls); return; }
     const uint32_t n = (uint32_t)g.size(), k = r0.th_k, nb = r0.th_nbytes, qb = r0.th_qbytes;
     // (CalculateR: a group (p, q) is one table row)
     std::map<std::string, uint32_t> slot;
@@ -993,6 +1029,20 @@ int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, ui
   r.th_shape = (uint64_t)11 | (uint64_t)dlen << 8 | (uint64_t)pbytes << 24 | (uint64_t)qbytes << 40;
   r.th_k = dlen; r.th_nbytes = pbytes; r.th_qbytes = qbytes; r.th_a = digest; r.th_b = sig; r.th_mod = p; r.th_mod2 = q; r.th_g = g; r.th_y = y;
   r.th_out = valid_out;
+  const int rc = b->submit(r);
+  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
+  if (rc) *valid_out = 0;
+  return rc;
+}
+
+int bftkv_gpu_batcher_dsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen, const uint8_t* sig,
+                                        uint8_t* valid_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (valid_out) *valid_out = 0;
+  if (!b || !status_out || !valid_out || !digest || !sig || dlen == 0 || dlen > 64) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r{12, keyset, nullptr, 0, nullptr, 0, false, 0};       // (an unknown handle fails its own group alone)
+  r.th_shape = (uint64_t)12 | (uint64_t)dlen << 8;
+  r.th_k = dlen; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
   const int rc = b->submit(r);
   *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
   if (rc) *valid_out = 0;

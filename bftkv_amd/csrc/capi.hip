@@ -107,6 +107,18 @@ struct EcKeySet {
   void release() { tab.release(); refused.release(); for (DevBuf& b : mod) b.release(); }
 };
 
+// A resident DSA key set (dsa_keyset_capi.inc): one fixed-base window table per distinct base, the groups' g first, then the keys' y
+struct DsaKeySet {
+  bool live = false;
+  uint32_t n_keys = 0, n_groups = 0, pbytes = 0, qbytes = 0;
+  uint32_t w = 0, windows = 0;             // window bits and ceil(max bits(q) / w)
+  DevBuf tab;                              // [n_groups + n_keys][windows][2^w - 1][76], fully reduced Montgomery entries (R = 2^2128)
+  DevBuf modp[3], modq[3];                 // n, R^2, -n^-1 rows of every p and q (the set's own copies: no call uploads anything)
+  DevBuf q_be, key_group;                  // [n_groups][qbytes] bytes; [n_keys] clamped group indices
+  uint64_t table_bytes() const { return (uint64_t)(n_groups + n_keys) * windows * ((1u << w) - 1u) * MONT_N * 4; }
+  void release() { tab.release(); q_be.release(); key_group.release(); for (DevBuf& b : modp) b.release(); for (DevBuf& b : modq) b.release(); }
+};
+
 }  // namespace
 
 using ctx_lock = std::lock_guard<std::recursive_mutex>;
@@ -163,6 +175,7 @@ struct bftkv_gpu_ctx {
 
   std::vector<QuorumHost> quorums;
   std::vector<EcKeySet> ec_keysets;    // root: the handles of bftkv_gpu_ecdsa_keyset_create; forks read them under KtRead, without a copy
+  std::vector<DsaKeySet> dsa_keysets;  // root: the handles of bftkv_gpu_dsa_keyset_create (a space of their own), read the same way
 
   // per-call arena
   DevBuf txt_mid32, txt_mid64, txt_tail, txt_len;     // text-mode hashing state (TextDev)
@@ -252,7 +265,7 @@ namespace {
 
 int fork_refresh(bftkv_gpu_ctx* c);
 
-// Exclusive access to the key table / quorum descriptors / ECDSA key sets of a root context (see bftkv_gpu_ctx::root).
+// Exclusive access to the key table / quorum descriptors / ECDSA and DSA key sets of a root context (see bftkv_gpu_ctx::root).
 struct KtWrite {
   bftkv_gpu_ctx* c;
   explicit KtWrite(bftkv_gpu_ctx* c_) : c(c_) { c->kt_writers.fetch_add(1); c->kt_rw.lock(); }
@@ -1276,6 +1289,7 @@ void bftkv_gpu_destroy(bftkv_gpu_ctx* c) {
     b->release();
   for (auto& q : c->quorums) { q.member.release(); q.ids.release(); }
   for (EcKeySet& ks : c->ec_keysets) ks.release();
+  for (DsaKeySet& ks : c->dsa_keysets) ks.release();
   c->in_pack.release();
   c->forced_iss.release();
   release_small_pin(c);
@@ -2331,6 +2345,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "threshold_capi.inc"
 #include "ec_capi.inc"
 #include "dsa_verify_capi.inc"
+#include "dsa_keyset_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

@@ -1,0 +1,203 @@
+// C ABI of resident DSA key sets (include/bftkv_gpu.h: bftkv_gpu_dsa_keyset_* and bftkv_gpu_dsa_verify_keyset; dsa_verify_kernels.hip).
+// A long-lived key (the distributed CA key of a threshold DSA signature) is registered once: the Montgomery rows of its group and a
+// fixed-base window table per distinct base are made at bftkv_gpu_dsa_keyset_create, and every verification after that is
+// k_dsav_prep and a chain of table products.  Sets live on the root context like quorums and ECDSA sets: created and destroyed
+// there under KtWrite (the forks' calls in flight drain first), read by the forks under KtRead without a copy.
+namespace {
+
+constexpr uint32_t DSA_KEYSET_MAX_KEYS = 4096, DSA_KEYSET_MAX_GROUPS = 4096;
+
+// caller holds c->mu and, on a fork, the root's key-table lock (KtRead)
+const DsaKeySet* dsa_keyset_find(const bftkv_gpu_ctx* c, int keyset) {
+  const bftkv_gpu_ctx* r = c->root ? c->root : c;
+  if (keyset < 0 || (size_t)keyset >= r->dsa_keysets.size() || !r->dsa_keysets[keyset].live) return nullptr;
+  return &r->dsa_keysets[keyset];
+}
+
+// chains of at most 256 entries: one part up to 8-bit windows, 2^(w - 8) beyond (k_dsav_comb_build)
+inline uint32_t dsa_keyset_parts(uint32_t w) { return w > 8 ? 1u << (w - 8) : 1u; }
+
+int dsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys_y, const uint32_t* key_group, uint32_t pbytes, uint32_t n_groups,
+                           const uint8_t* p, const uint8_t* q, const uint8_t* g, uint32_t qbytes, uint32_t window_bits, int* keyset_out) {
+  if (!c || !keys_y || !p || !q || !g || !keyset_out || n_keys == 0 || n_keys > DSA_KEYSET_MAX_KEYS || n_groups == 0 || n_groups > DSA_KEYSET_MAX_GROUPS ||
+      pbytes == 0 || pbytes > 256 || qbytes == 0 || qbytes > 32 || (window_bits != 0 && (window_bits < DSAV_COMB_WMIN || window_bits > DSAV_COMB_WMAX)))
+    return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  if (c->root) return fail(c, BFTKV_E_STATE, "DSA key sets are created on the root context; its forks see them");
+  HIPCHK(c, hipSetDevice(c->device));
+  ScratchBufs sb(c);
+  { int grc = modtab_gc(c); if (grc) return grc; }
+  DsaKeySet ks;
+  int rc = 0;
+  auto nomem = [&]() { (void)hipGetLastError(); return fail(c, BFTKV_E_NOMEM, "DSA key set: device allocation failed"); };
+  auto build = [&]() -> int {
+    ks.n_keys = n_keys; ks.n_groups = n_groups; ks.pbytes = pbytes; ks.qbytes = qbytes;
+    ks.w = window_bits ? window_bits : DSAV_COMB_WDEF;
+    uint32_t max_qbits = 1;
+    for (uint32_t i = 0; i < n_groups; ++i) max_qbits = std::max(max_qbits, (uint32_t)hostbn::bit_length(q + (size_t)i * qbytes, qbytes));
+    ks.windows = dsav_comb_windows(max_qbits, ks.w);
+    // the rows of every p and q, copied out of the context's cache (which may drop them) into the set
+    ModTab mp, mq;
+    if ((rc = make_modtab(c, sb, p, n_groups, pbytes, &mp))) return rc;          // (an even p or q: BFTKV_E_UNSUPPORTED, no set)
+    if ((rc = make_modtab(c, sb, q, n_groups, qbytes, &mq))) return rc;
+    const size_t len[3] = {(size_t)n_groups * MONT_N * 4, (size_t)n_groups * MONT_N * 4, (size_t)n_groups * 4};
+    const void* srcp[3] = {mp.n_limbs, mp.r2_limbs, mp.n0inv};
+    const void* srcq[3] = {mq.n_limbs, mq.r2_limbs, mq.n0inv};
+    for (int k = 0; k < 3; ++k) {
+      if (ks.modp[k].ensure_exact(len[k]) != hipSuccess || ks.modq[k].ensure_exact(len[k]) != hipSuccess) return nomem();
+      HIPCHK(c, hipMemcpyAsync(ks.modp[k].p, srcp[k], len[k], hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(ks.modq[k].p, srcq[k], len[k], hipMemcpyDeviceToDevice, c->stream));
+    }
+    std::vector<uint32_t> kg(n_keys, 0u);
+    if (key_group) for (uint32_t k = 0; k < n_keys; ++k) kg[k] = std::min(key_group[k], n_groups - 1u);
+    if (ks.q_be.ensure_exact((size_t)n_groups * qbytes) != hipSuccess || ks.key_group.ensure_exact((size_t)n_keys * 4) != hipSuccess ||
+        ks.tab.ensure_exact(ks.table_bytes()) != hipSuccess)
+      return nomem();
+    HIPCHK(c, hipMemcpyAsync(ks.q_be.p, q, (size_t)n_groups * qbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ks.key_group.p, kg.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, c->stream));
+    // the bases, g of every group and then y of every key, as one array of limbs (scratch of this call)
+    const uint32_t n_bases = n_groups + n_keys;
+    std::vector<uint8_t> bases((size_t)n_bases * pbytes);
+    memcpy(bases.data(), g, (size_t)n_groups * pbytes);
+    memcpy(bases.data() + (size_t)n_groups * pbytes, keys_y, (size_t)n_keys * pbytes);
+    uint32_t* d_bases;
+    if ((rc = to_dev_limbs(c, sb, bases.data(), n_bases, pbytes, &d_bases))) return rc;
+    const ModTab sp{ks.modp[0].as<uint32_t>(), ks.modp[1].as<uint32_t>(), ks.modp[2].as<uint32_t>(), nullptr};
+    const uint32_t parts = dsa_keyset_parts(ks.w);
+    hipLaunchKernelGGL((k_dsav_comb_build<MONT_L, MONT_TPI>), quad_grid(n_bases * ks.windows * parts), dim3(RSA_BLOCK), 0, c->stream, n_groups, n_keys,
+                       (const uint32_t*)d_bases, ks.key_group.as<uint32_t>(), sp, ks.w, ks.windows, parts, ks.tab.as<uint32_t>());
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (the host vectors above die with this call)
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  };
+  rc = build();
+  if (rc) { (void)hipStreamSynchronize(c->stream); ks.release(); return rc; }
+  ks.live = true;
+  int h = -1;
+  for (size_t i = 0; i < c->dsa_keysets.size(); ++i) if (!c->dsa_keysets[i].live) { h = (int)i; break; }
+  KtWrite kw(c);
+  if (h < 0) { c->dsa_keysets.emplace_back(); h = (int)c->dsa_keysets.size() - 1; }
+  c->dsa_keysets[h] = std::move(ks);
+  *keyset_out = h;
+  return 0;
+}
+
+int dsa_keyset_destroy_impl(bftkv_gpu_ctx* c, int keyset) {
+  if (!c) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  if (c->root) return fail(c, BFTKV_E_STATE, "DSA key sets are destroyed on the root context");
+  if (!dsa_keyset_find(c, keyset)) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
+  HIPCHK(c, hipSetDevice(c->device));
+  KtWrite kw(c);
+  HIPCHK(c, hipDeviceSynchronize());          // (_dev calls return before their kernels have run: nothing may still read the tables)
+  c->dsa_keysets[keyset].release();
+  c->dsa_keysets[keyset] = DsaKeySet();
+  return 0;
+}
+
+int dsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_groups_out, uint32_t* pbytes_out, uint32_t* qbytes_out,
+                         uint32_t* window_bits_out, uint32_t* windows_out, uint64_t* table_bytes_out) {
+  if (!c) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const DsaKeySet* ks = dsa_keyset_find(c, keyset);
+  if (!ks) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
+  if (n_keys_out) *n_keys_out = ks->n_keys;
+  if (n_groups_out) *n_groups_out = ks->n_groups;
+  if (pbytes_out) *pbytes_out = ks->pbytes;
+  if (qbytes_out) *qbytes_out = ks->qbytes;
+  if (window_bits_out) *window_bits_out = ks->w;
+  if (windows_out) *windows_out = ks->windows;
+  if (table_bytes_out) *table_bytes_out = ks->table_bytes();
+  return 0;
+}
+
+// one base's table, as built (test hook); bases count the groups' g first, then the keys' y
+int dsa_keyset_table_impl(bftkv_gpu_ctx* c, int keyset, uint32_t base, uint32_t* words_out, uint64_t cap_words) {
+  if (!c || !words_out) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const DsaKeySet* ks = dsa_keyset_find(c, keyset);
+  if (!ks || base >= ks->n_groups + ks->n_keys) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle or base index");
+  const uint64_t words = ks->table_bytes() / 4 / (ks->n_groups + ks->n_keys);
+  if (cap_words < words) return fail(c, BFTKV_E_NOMEM, "words_out holds less than one table");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(words_out, ks->tab.as<uint32_t>() + (size_t)base * words, words * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// dsa_verify_impl over a registered set: the same k_dsav_prep, then k_dsav_comb_exp.  Nothing is read from host memory but the host
+// form's own arrays (the rows, the orders, the groups and the tables are resident), so the device form never waits.
+int dsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                           const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out, bool dev) {
+  if (!c || n_ops > DSAV_MAX_OPS || (n_ops && (!valid_out || !status_out))) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if (n_ops) {                                 // fail closed: whatever refuses the call below leaves failures behind
+    if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
+    if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
+    else memset(valid_out, 0, n_ops);
+  }
+  if (dlen == 0 || dlen > 64 || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const DsaKeySet* ks = dsa_keyset_find(c, keyset);
+  if (!ks) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
+  if (n_ops == 0) return 0;
+  ScratchBufs sb(c);
+  const ModTab mp{ks->modp[0].as<uint32_t>(), ks->modp[1].as<uint32_t>(), ks->modp[2].as<uint32_t>(), nullptr};
+  const ModTab mq{ks->modq[0].as<uint32_t>(), ks->modq[1].as<uint32_t>(), ks->modq[2].as<uint32_t>(), nullptr};
+  uint32_t* d_ki = nullptr;
+  uint8_t *d_dg, *d_sig;
+  void *d_e, *d_ok, *d_og, *d_flag, *d_valid, *d_st;
+  if (key_idx && (rc = to_dev(c, sb, key_idx, (size_t)n_ops, &d_ki, dev))) return rc;                  // clamped by k_dsav_prep
+  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
+  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * ks->qbytes, &d_sig, dev))) return rc;
+  if ((rc = dev_alloc(c, sb, (size_t)n_ops * DSAV_ROW * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * 4, &d_ok, false)) ||
+      (rc = dev_alloc(c, sb, (size_t)n_ops * 4, &d_og, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)))
+    return rc;
+  if (dev) { d_valid = valid_out; d_st = status_out; }
+  else if ((rc = dev_alloc(c, sb, n_ops, &d_valid, false)) || (rc = dev_alloc(c, sb, n_ops, &d_st, false))) return rc;
+  hipStream_t s = c->stream;
+  hipLaunchKernelGGL(k_dsav_prep, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint8_t*)d_dg, dlen, (const uint8_t*)d_sig, ks->qbytes,
+                     (const uint32_t*)d_ki, ks->n_keys, ks->key_group.as<uint32_t>(), ks->q_be.as<uint8_t>(), (uint32_t*)d_e, (uint32_t*)d_ok,
+                     (uint32_t*)d_og, (uint8_t*)d_flag, (uint8_t*)d_st);
+  hipLaunchKernelGGL((k_dsav_comb_exp<MONT_L, MONT_TPI>), quad_grid(n_ops), dim3(RSA_BLOCK), 0, s, n_ops, (const uint32_t*)d_e, (const uint32_t*)d_ok,
+                     (const uint32_t*)d_og, (const uint8_t*)d_flag, ks->n_groups, mp, mq, ks->tab.as<uint32_t>(), ks->w, ks->windows, (uint8_t*)d_valid);
+  if (!dev) {
+    HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
+  }
+  return finish(c, dev);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bftkv_gpu_dsa_keyset_create(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys_y, const uint32_t* key_group, uint32_t pbytes, uint32_t n_groups,
+                                const uint8_t* p, const uint8_t* q, const uint8_t* g, uint32_t qbytes, uint32_t window_bits, int* keyset_out) {
+  return dsa_keyset_create_impl(c, n_keys, keys_y, key_group, pbytes, n_groups, p, q, g, qbytes, window_bits, keyset_out);
+}
+int bftkv_gpu_dsa_keyset_destroy(bftkv_gpu_ctx* c, int keyset) { return dsa_keyset_destroy_impl(c, keyset); }
+int bftkv_gpu_dsa_keyset_info(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_groups_out, uint32_t* pbytes_out, uint32_t* qbytes_out,
+                              uint32_t* window_bits_out, uint32_t* windows_out, uint64_t* table_bytes_out) {
+  return dsa_keyset_info_impl(c, keyset, n_keys_out, n_groups_out, pbytes_out, qbytes_out, window_bits_out, windows_out, table_bytes_out);
+}
+int bftkv_gpu_dsa_verify_keyset(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out) {
+  return dsa_verify_keyset_impl(c, keyset, n_ops, digests, dlen, sigs, key_idx, valid_out, status_out, false);
+}
+int bftkv_gpu_dsa_verify_keyset_dev(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                    const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out) {
+  return dsa_verify_keyset_impl(c, keyset, n_ops, digests, dlen, sigs, key_idx, valid_out, status_out, true);
+}
+int bftkv_gpu_selftest_dsa_keyset_table(bftkv_gpu_ctx* c, int keyset, uint32_t base, uint32_t* words_out, uint64_t cap_words) {
+  return dsa_keyset_table_impl(c, keyset, base, words_out, cap_words);
+}
+
+}  // extern "C"

@@ -67,4 +67,26 @@ U256_HD void dsav_prep_one(const uint8_t* sig, uint32_t qbytes, const uint8_t* q
   o.status = fenced ? DSAV_FENCED : ((live && !inv) ? DSAV_NO_INVERSE : DSAV_OK);
 }
 
+// ---- resident key sets (bftkv_gpu_dsa_keyset_*): fixed-base window tables, tab[base][window][d - 1][76 limbs] ----------------
+// Window i of an exponent is its bits [w i, w i + w), w = 4 .. 16, read out of dsav_limbs10's ten limbs: at w = 4, 7 and 14 a
+// window lies within one limb, at every other width some windows straddle two.  The top window is narrower when w does not
+// divide the order's length (its high digits never occur; the table holds 2^w - 1 entries for it all the same).
+constexpr uint32_t DSAV_COMB_WMIN = 4, DSAV_COMB_WMAX = 16, DSAV_COMB_WDEF = 8;
+constexpr uint32_t DSAV_COMB_ENTRY_LIMBS = 76;                            // MONT_N of mont28.h: the <19, 4> form, R = 2^2128
+
+U256_HD uint32_t dsav_comb_windows(uint32_t qbits, uint32_t w) { return (qbits + w - 1u) / w; }
+
+U256_HD uint32_t dsav_comb_digit(const uint32_t* limbs10, uint32_t window, uint32_t w) {
+  const uint32_t bit = window * w, li = bit / 28u, sh = bit % 28u;
+  if (li >= (uint32_t)DSAV_EXP_LIMBS) return 0u;
+  uint64_t v = limbs10[li];
+  if (li + 1u < (uint32_t)DSAV_EXP_LIMBS) v |= (uint64_t)limbs10[li + 1u] << 28;
+  return (uint32_t)(v >> sh) & ((1u << w) - 1u);
+}
+
+// the entry of digit d >= 1 in window `window` of base `base`, counted in entries (76 limbs each)
+U256_HD uint64_t dsav_comb_entry(uint32_t base, uint32_t window, uint32_t d, uint32_t windows, uint32_t w) {
+  return ((uint64_t)base * windows + window) * ((1u << w) - 1u) + (d - 1u);
+}
+
 }  // namespace bftkv

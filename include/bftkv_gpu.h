@@ -408,6 +408,13 @@ int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint
 int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, uint32_t qbytes,
                                  const uint8_t* y, uint32_t pbytes, const uint8_t* p, const uint8_t* q, const uint8_t* g, uint8_t* valid_out,
                                  uint8_t* status_out);
+/* The same for ONE signature under key `key` of a resident DSA key set (bftkv_gpu_dsa_keyset_create on the batcher's context):
+ * digest [dlen], sig [2 qbytes of the set]; an index past the set is clamped to its last key.  Callers are grouped by key set and
+ * digest length.  An unknown or destroyed handle, or a dlen outside 1 .. 64, returns BFTKV_E_INVALID for that caller alone; whenever
+ * the return code is not 0, *status_out is BFTKV_TH_FAILED and *valid_out 0.  The lane reads 2 qbytes of `sig` for the set the
+ * handle names when the request RUNS: the caller must not destroy a set while calls that name it are in flight. */
+int bftkv_gpu_batcher_dsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen,
+                                        const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -646,6 +653,47 @@ int bftkv_gpu_ecdsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n
 /* Diagnostic: the table of key `key` of a set as the device built it, fb_table_words (windows x 2 L x 2^w) 32-bit words; all zero
  * for a refused key.  BFTKV_E_NOMEM when cap_words is less than that.  The tests compare it with the host-built table. */
 int bftkv_gpu_selftest_ecdsa_keyset_table(bftkv_gpu_ctx* ctx, int keyset, uint32_t key, uint32_t* words_out, uint64_t cap_words);
+
+/* Resident DSA key sets: the groups and keys of bftkv_gpu_dsa_verify registered once, for callers whose keys outlive a call (the
+ * distributed CA key of a threshold DSA signature).  keys_y [n_keys][pbytes], key_group [n_keys] (NULL: group 0; an index past the
+ * groups is clamped), p, g [n_groups][pbytes], q [n_groups][qbytes] as for that entry: pbytes <= 256, qbytes <= 32 (fixed for the
+ * set's life: signatures are [n_ops][2 qbytes]), 1 <= n_keys <= 4096, 1 <= n_groups <= 4096.  window_bits is 4 .. 16, or 0 for the
+ * default of 8; any other value is BFTKV_E_INVALID, as are a NULL array, a zero count and a width out of range.  A group with an
+ * even p or an even q is BFTKV_E_UNSUPPORTED: no set is made and *keyset_out is untouched.
+ * The set holds, all on the device: the Montgomery rows of every p and q (its own copies, so that a verification uploads nothing),
+ * the orders, the keys' clamped groups, and one fixed-base window table per base -- the n_groups generators first, then the n_keys
+ * public values: tab[base][window i][d - 1] = b^(d 2^(w i)) R mod p for d = 1 .. 2^w - 1, 76 limbs of 28 bits (R = 2^2128), fully
+ * reduced (below p, every limb below 2^28), with windows = ceil(max bits(q) / w).  A base >= p (0 and p included) is reduced as
+ * bftkv_gpu_dsa_verify reduces it.  Per base under a 256-bit q: 292 KB at w = 4, 2.5 MB at 8, 27 MB at 12, 319 MB at 16; the
+ * caller picks the width.  Like quorums and ECDSA sets, DSA sets are created and destroyed on the root context (a fork:
+ * BFTKV_E_STATE; the root waits for its forks' calls in flight) and read by its forks and batcher lanes; bftkv_gpu_destroy
+ * releases what is left.  A failed device allocation is BFTKV_E_NOMEM, with nothing left allocated; an unknown or destroyed handle
+ * BFTKV_E_INVALID.  DSA handles are a space of their own (as quorums and ECDSA sets are).  A destroyed handle is handed out again by
+ * a later create, so retire a set only when no call that names it is in flight (batcher calls included: they size the signature by
+ * the set they find when they run). */
+int bftkv_gpu_dsa_keyset_create(bftkv_gpu_ctx* ctx, uint32_t n_keys, const uint8_t* keys_y, const uint32_t* key_group, uint32_t pbytes,
+                                uint32_t n_groups, const uint8_t* p, const uint8_t* q, const uint8_t* g, uint32_t qbytes, uint32_t window_bits,
+                                int* keyset_out);
+int bftkv_gpu_dsa_keyset_destroy(bftkv_gpu_ctx* ctx, int keyset);
+/* any of the outputs may be NULL; table_bytes_out = (n_groups + n_keys) x windows x (2^w - 1) x 304 */
+int bftkv_gpu_dsa_keyset_info(bftkv_gpu_ctx* ctx, int keyset, uint32_t* n_keys_out, uint32_t* n_groups_out, uint32_t* pbytes_out,
+                              uint32_t* qbytes_out, uint32_t* window_bits_out, uint32_t* windows_out, uint64_t* table_bytes_out);
+/* bftkv_gpu_dsa_verify under the keys of a set: for every input the same (valid, status) as that entry gives for the same digest and
+ * signature bytes under the same (p, q, g, y) -- row by row of the table in docs/parity.md "DSA verification", fenced winning over
+ * no-inverse -- with g^u1 y^u2 taken from the tables as a chain of at most 2 windows - 1 products and no squarings.  key_idx [n_ops]
+ * indexes the set (NULL: key 0, an index past the set is clamped to its last key); sigs are [n_ops][2 qbytes] of the set;
+ * 1 <= dlen <= 64.  Whenever the return code is not 0 (a bad handle included) every status is BFTKV_TH_FAILED and every verdict 0;
+ * nothing past n_ops is written; n_ops = 0 returns 0. */
+int bftkv_gpu_dsa_verify_keyset(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+/* same with digests / sigs / key_idx / valid_out / status_out resident in HBM: nothing is read from host memory, so the call is
+ * asynchronous on the context's stream and never waits for it. */
+int bftkv_gpu_dsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
+                                    const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+/* Diagnostic: the table of base `base` of a set (the groups' g first, then the keys' y) as the device built it, windows x (2^w - 1)
+ * x 76 32-bit words.  BFTKV_E_NOMEM when cap_words is less than that, BFTKV_E_INVALID for a base past the set.  The tests compare
+ * it with a table built by pow(). */
+int bftkv_gpu_selftest_dsa_keyset_table(bftkv_gpu_ctx* ctx, int keyset, uint32_t base, uint32_t* words_out, uint64_t cap_words);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

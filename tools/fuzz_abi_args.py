@@ -336,6 +336,70 @@ def ecdsa_keyset_calls():
     note("ecdsa_keyset_destroy", lib.bftkv_gpu_ecdsa_keyset_destroy(ctx, rng.choice([-1, hs.value, 3, 2 ** 31 - 1])))
 
 
+def dsa_keyset_calls():
+    """The DSA key-set entries: create (any group and key bytes, odd moduli most of the time), info, the test hook, verification
+    through the handle (host form, _dev form only where it is refused or has no operations, batcher) and destroy, with live, stale
+    and made-up handles.  Whatever comes back, a non-zero return leaves failures and no verdict."""
+    pb = rng.choice([0, 1, 64, 128, 256, 257])
+    qb = rng.choice([0, 1, 20, 28, 32, 33])
+    n_keys, n_groups = rng.choice([0, 1, 1, 2, 5, 4097]), rng.choice([0, 1, 1, 3, 4097])
+    w = rng.choice([0, 0, 3, 4, 4, 5, 6, 17])             # (narrow windows: the tables stay small)
+    y, p, q, g = buf(max(n_keys, 1) * pb), buf(max(n_groups, 1) * pb), buf(max(n_groups, 1) * qb), buf(max(n_groups, 1) * pb)
+    if rng.random() < 0.7:
+        for arr, wd in ((p, pb), (q, qb)):
+            if wd:
+                arr[wd - 1::wd] |= 1
+    kg = np.array([rng.choice([0, 1, n_groups, 2 ** 32 - 1]) for _ in range(max(n_keys, 1))], dtype=np.uint32)
+    kgp = kg.ctypes.data_as(vp) if rng.random() < 0.5 else None
+    hs = C.c_int(-9)
+    rc = lib.bftkv_gpu_dsa_keyset_create(ctx, n_keys, p8(y), kgp, pb, n_groups, p8(p), p8(q), p8(g), qb, w, C.byref(hs))
+    assert (rc == 0) == (hs.value >= 0), ("dsa_keyset_create", rc, hs.value)
+    note("dsa_keyset_create", rc)
+    live = rc == 0
+    handle = hs.value if live and rng.random() < 0.8 else rng.choice([-1, 0, 1, 7, 2 ** 31 - 1])
+    v = [C.c_uint32() for _ in range(6)]
+    tb = C.c_uint64()
+    rc = lib.bftkv_gpu_dsa_keyset_info(ctx, handle, *[C.byref(x) for x in v], C.byref(tb))
+    nk, ng, ipb, iqb, iw, nwin = (x.value for x in v)
+    assert rc != 0 or (1 <= nk <= 4096 and 1 <= ng <= 4096 and 1 <= ipb <= 256 and 1 <= iqb <= 32 and 4 <= iw <= 16 and
+                       tb.value == (nk + ng) * nwin * ((1 << iw) - 1) * 304), ("dsa_keyset_info", nk, ng, ipb, iqb, iw, nwin, tb.value)
+    note("dsa_keyset_info", rc)
+    known = rc == 0
+    sq = iqb if known else 32                              # signatures sized for the set the handle names, else for the widest order
+    words = np.zeros(rng.choice([0, 8, 400000]), dtype=np.uint32)
+    note("selftest_dsa_keyset_table", lib.bftkv_gpu_selftest_dsa_keyset_table(ctx, handle, rng.choice([0, 1, 8192]), words.ctypes.data_as(vp), len(words)))
+    n_ops = rng.choice([0, 1, 2, 5, 64])
+    dlen = rng.choice([0, 1, 20, 32, 64, 65, 4096])
+    dg, sg = buf(n_ops * min(dlen, 4096)), buf(n_ops * 2 * sq)
+    ki = np.array([rng.choice([0, 1, n_keys, 2 ** 32 - 1]) for _ in range(max(n_ops, 1))], dtype=np.uint32)
+    kip = ki.ctypes.data_as(vp) if rng.random() < 0.5 else None
+    valid, st = buf(n_ops, "zero"), buf(n_ops, "zero")
+    which = rng.randrange(3)
+    if which == 0:
+        rc = lib.bftkv_gpu_dsa_verify_keyset(ctx, handle, n_ops, p8(dg), dlen, p8(sg), kip, p8(valid), p8(st))
+        assert rc == 0 or (not valid[:n_ops].any() and (st[:n_ops] == 0xFF).all()), ("dsa_verify_keyset", rc)      # fail closed
+        assert rc != 0 or known, ("dsa_verify_keyset", handle)
+        note("dsa_verify_keyset", rc)
+    elif which == 1:
+        if rng.random() < 0.5:
+            n_ops = 0
+        else:
+            dlen = rng.choice([0, 65, 4096])
+            valid, st = None, None                      # (refused before anything is written: the arrays would have to live in HBM)
+        note("dsa_verify_keyset_dev", lib.bftkv_gpu_dsa_verify_keyset_dev(ctx, handle, n_ops, p8(dg), dlen, p8(sg), kip,
+                                                                         p8(valid) if valid is not None else None, p8(st) if st is not None else None))
+    else:
+        v1, s1 = C.c_uint8(0x55), C.c_uint8(0x55)
+        rc = lib.bftkv_gpu_batcher_dsa_verify_keyset(batcher, handle, rng.choice([0, 1, 2 ** 32 - 1]), p8(buf(min(dlen, 4096))), dlen, p8(buf(2 * sq)),
+                                                     C.byref(v1), C.byref(s1))
+        assert rc == 0 or (s1.value == 0xFF and v1.value == 0), ("batcher_dsa_verify_keyset", rc, s1.value, v1.value)      # fail closed
+        note("batcher_dsa_verify_keyset", rc)
+    if live:
+        rc = lib.bftkv_gpu_dsa_keyset_destroy(ctx, hs.value)
+        assert rc == 0, ("dsa_keyset_destroy", rc)
+    note("dsa_keyset_destroy", lib.bftkv_gpu_dsa_keyset_destroy(ctx, rng.choice([-1, hs.value, 3, 2 ** 31 - 1])))
+
+
 def offsets(n, total):
     o = np.zeros(n + 1, dtype=np.uint64)
     style = rng.random()
@@ -491,7 +555,7 @@ t0 = time.time()
 n = 0
 while time.time() - t0 < budget:
     rng.choice([threshold_batched, threshold_batched, threshold_one, verify_calls, verify_calls, keyring_and_quorum, cert_calls, cert_calls,
-                ecdsa_calls, ecdsa_verify_calls, ecdsa_keyset_calls, dsa_verify_calls])()
+                ecdsa_calls, ecdsa_verify_calls, ecdsa_keyset_calls, dsa_verify_calls, dsa_keyset_calls])()
     n += 1
 lib.bftkv_gpu_batcher_destroy(batcher)
 lib.bftkv_gpu_destroy(ctx)

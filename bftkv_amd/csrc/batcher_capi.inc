@@ -36,7 +36,7 @@ namespace {
 //   [ midstates n x 8 u32 | prefix n u64 | tail offsets n+1 u64 | signature offsets n+1 u64 | entity indices n u32 |
 //     payload tails (< 64 B each) | signature streams ]
 struct StagedCall {
-  int kind = 0;              // 0 CollectiveSignature.Verify, 1 Signature.Verify / VerifyWithCertificate
+  bool collective = true;    // CollectiveSignature.Verify; false: Signature.Verify / VerifyWithCertificate
   int quorum = -1;
   uint32_t n = 0;
   bool has_cert = false;
@@ -115,7 +115,7 @@ int staged_verify(bftkv_gpu_ctx* c, const StagedCall& L, uint8_t* pin, const uin
   // Every packet of every item is verified (no two-phase planning): err and n_verified are the reference's either way, a
   // small call is bound by its chain of launches, not by the 20 % of modexps the planning saves, and it is seven launches
   // shorter.
-  if (L.kind == 0) {
+  if (L.collective) {
     if ((rc = check_quorum(c, L.quorum))) return rc;
     QuorumHost& q = c->quorums[L.quorum];
     if ((rc = build_member(c, q))) return rc;
@@ -182,7 +182,7 @@ struct StagedItem {
 // Assembles a group in `pin` and runs it (staged_verify); the items whose signatures ask for a hash other than SHA-256, or a
 // whole call with more packet events than the staged arena holds, go through the ordinary entry points with their payloads.
 // err / fenced: per item.  device_calls counts what was launched.
-int staged_group(bftkv_gpu_ctx* c, PinnedBuf& pin, PinnedBuf& pin_tb, PinnedBuf& pin_sb, int kind, int quorum, bool has_cert,
+int staged_group(bftkv_gpu_ctx* c, PinnedBuf& pin, PinnedBuf& pin_tb, PinnedBuf& pin_sb, bool collective, int quorum, bool has_cert,
                  const std::vector<StagedItem>& g, uint8_t* err, uint8_t* fenced, uint8_t failing, uint64_t* device_calls,
                  uint64_t* ns_assemble = nullptr, uint64_t* ns_device = nullptr, uint64_t* ns_launch = nullptr, uint64_t* ns_spin = nullptr,
                  uint64_t* n_timeouts = nullptr, uint8_t* unresolved = nullptr) {
@@ -191,7 +191,7 @@ int staged_group(bftkv_gpu_ctx* c, PinnedBuf& pin, PinnedBuf& pin_tb, PinnedBuf&
   uint64_t tails = 0, sl = 0;
   for (const StagedItem& r : g) { tails += r.tbs_len & 63; sl += r.sig_len; }
   StagedCall L;
-  L.kind = kind; L.quorum = quorum; L.has_cert = has_cert;
+  L.collective = collective; L.quorum = quorum; L.has_cert = has_cert;
   L.layout(n, tails, sl);
   std::vector<uint8_t> flags(n, 0);
   std::vector<uint64_t> certs(n, 0);
@@ -250,7 +250,7 @@ int staged_group(bftkv_gpu_ctx* c, PinnedBuf& pin, PinnedBuf& pin_tb, PinnedBuf&
       if (r.tbs_len) memcpy(pin_tb.p + to2[j], r.tbs, r.tbs_len);
       if (r.sig_len) memcpy(pin_sb.p + so2[j], r.sig, r.sig_len);
     }
-    if (kind == 0)
+    if (collective)
       rc2 = bftkv_gpu_collective_verify(c, quorum, m, pin_tb.p, to2.data(), pin_sb.p, so2.data(), e2.data(), nullptr, nullptr, f2.data());
     else
       rc2 = bftkv_gpu_signature_verify(c, m, pin_tb.p, to2.data(), pin_sb.p, so2.data(), has_cert ? c2.data() : nullptr, e2.data(), f2.data());
@@ -274,44 +274,66 @@ inline void batch_futex_wake_all(std::atomic<uint32_t>* w) {
 }
 
 struct bftkv_gpu_batcher {
+  // What a request asks for.  Requests of one batch that agree in (kind, quorum, has_cert, th_shape) share a device call (process).
+  enum class Kind {
+    Collective, Signature, Message, Cert,                      // CollectiveSignature.Verify, Signature.Verify, a transport message, Issuer + VerifyWithCertificate
+    ModmulProduct, LagrangeCombine, DsaCalculateR, Modexp,     // ONE share-combine operation: prod psig mod N, sum l_j y_j mod m, CalculateR, b^x mod n
+    EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset
+  };
+  static bool hashed_by_caller(Kind k) { return k == Kind::Collective || k == Kind::Signature; }      // a SHA-256 midstate of tbs goes to the device, not tbs
+  static bool threshold_style(Kind k) { return k >= Kind::ModmulProduct; }      // th_* fields in, a BFTKV_TH_* status byte and th_out out
+  static constexpr int NO_QUORUM = -1;       // Req::quorum of the kinds that name neither a quorum nor a key set
+
+  // The fields by kind (f = the curve's field bytes, pb / qb = the bytes of p / q, dlen = the digest's length, curve = P|N|B|Gx|Gy, verdict = one
+  // byte, th_out otherwise that many output bytes; in a key-set kind f / qb are the set's; "-": unused):
+  //   kind                      quorum  th_k  th_nbytes  th_qbytes  th_xs  th_a            th_b        th_mod  th_mod2        th_g, th_y  ks_key  th_out
+  //   Collective                quorum  -     -          -          -      -               -           -       -              -           -       -
+  //   Signature, Message, Cert  -       -     -          -          -      -               -           -       -              -           -       -
+  //   ModmulProduct             -       k     nbytes     0          -      k factors       -           N       -              -           -       nbytes
+  //   LagrangeCombine           -       k     nbytes     0          k x_j  k y_j           -           m       -              -           -       nbytes
+  //   DsaCalculateR             -       k     pb         qb         k x_j  k Ri (pb)       k Vi (qb)   p       q              -           -       qb
+  //   Modexp                    -       1     nbytes     exp bytes  -      base            exponent    n       -              -           -       nbytes
+  //   EcdsaCalculateR           -       k     f          bit size   k x_j  k Ri (1 + 2 f)  k Vi (f)    curve   -              -           -       f
+  //   EcdsaVerify               -       dlen  f          bit size   -      digest          r|s (2 f)   curve   key (1 + 2 f)  -           -       verdict
+  //   EcdsaVerifyKeyset         set     dlen  -          -          -      digest          r|s (2 f)   -       -              -           key     verdict
+  //   DsaVerify                 -       dlen  pb         qb         -      digest          r|s (2 qb)  p       q              g, y (pb)   -       verdict
+  //   DsaVerifyKeyset           set     dlen  -          -          -      digest          r|s (2 qb)  -       -              -           key     verdict
+  // An EcdsaCalculateR or EcdsaVerify group shares one recognised curve, which the device call takes by value: its bit size is part of
+  // the shape.  A key-set group shares the set: the lane is a fork and passes the handle through.
   struct Req {
-    int kind;                  // 0 collective verify, 1 signature verify, 2 transport message (tbs = the packet sequence),
-                               // 3 Issuer + VerifyWithCertificate over a request certificate (cert / cert_len below),
-                               // 4..7 ONE threshold share-combine operation (th_* below): 4 prod psig mod N, 5 sum l_j y_j mod m,
-                               // 6 CalculateR, 7 b^x mod n, 8 ECDSA CalculateR, 9 ECDSA verification (key in the call),
-                               // 10 ECDSA verification under a resident key set (quorum = the set's handle), 11 DSA verification
-                               // (group and key in the call)
+    Kind kind;
     int quorum;
     const uint8_t* tbs; uint64_t tbs_len;
     const uint8_t* sig; uint64_t sig_len;
     bool has_cert; uint64_t cert_key_id;
     // Results start out as FAILURES: a caller that looks at the status byte and not at the return code (or a group whose
-    // device call failed) must never read "verified".  kind 0: BFTKV_ERR_INSUFFICIENT_SIGNATURES, kind 1:
-    // BFTKV_ERR_INVALID_SIGNATURE, kind 2: BFTKV_MSG_READ_ERROR.
+    // device call failed) must never read "verified".
     uint8_t err = BFTKV_ERR_INVALID_SIGNATURE; int rc = BFTKV_E_STATE;
     uint8_t fenced = 0;
-    static uint8_t failing(int kind) {
-      return kind >= 4 ? (uint8_t)BFTKV_TH_FAILED : kind == 0 ? BFTKV_ERR_INSUFFICIENT_SIGNATURES : (kind == 1 || kind == 3) ? BFTKV_ERR_INVALID_SIGNATURE : BFTKV_MSG_READ_ERROR;
+    static uint8_t failing(Kind k) {
+      if (threshold_style(k)) return BFTKV_TH_FAILED;
+      return k == Kind::Collective ? BFTKV_ERR_INSUFFICIENT_SIGNATURES : k == Kind::Message ? BFTKV_MSG_READ_ERROR : BFTKV_ERR_INVALID_SIGNATURE;
     }
-    // kind 3
+    // requests of one SHAPE (kind, k or dlen, widths) share a device call, whatever their moduli, groups and keys
+    static uint64_t shape(Kind k, uint64_t a, uint64_t b = 0, uint64_t c = 0) { return (uint64_t)k | a << 8 | b << 24 | c << 40; }
+    // Cert
     const uint8_t* cert = nullptr; uint64_t cert_len = 0, issuer_id = 0;
-    // kind 1 on behalf of bftkv_gpu_batcher_cert_verify: the entity is the one registered for a certificate the root has accepted
-    // before (its group and the epoch of that answer); unresolved = 1: no verdict from this route, ask the compound one (kind 3)
+    // Signature on behalf of bftkv_gpu_batcher_cert_verify: the entity is the one registered for a certificate the root has accepted
+    // before (its group and the epoch of that answer); unresolved = 1: no verdict from this route, ask the compound one (Cert)
     int cert_group = -1; uint64_t cert_epoch = 0; uint8_t unresolved = 0;
-    // kind 2 results
+    // Message results
     uint8_t* plain_out = nullptr; uint64_t plain_cap = 0, plain_len = 0, signer = 0, peer = 0;
     uint8_t* fname_out = nullptr; uint8_t fname_len = 0;
-    // kinds 0 / 1: SHA-256 state after the whole blocks of tbs, absorbed by the caller's own thread in submit()
+    // hashed_by_caller: SHA-256 state after the whole blocks of tbs, absorbed by the caller's own thread in submit()
     uint32_t mid[8] = {};
-    // kinds 4..10: one operation of th_k terms over numbers of th_nbytes (th_qbytes: the order's width for CalculateR, the exponent's
-    // for kind 7); requests of one SHAPE (kind, k, widths) share a device call, whatever their moduli
+    // threshold_style (the table above)
     uint64_t th_shape = 0;
     uint32_t th_k = 0, th_nbytes = 0, th_qbytes = 0;
     const int32_t* th_xs = nullptr;
     const uint8_t *th_a = nullptr, *th_b = nullptr, *th_mod = nullptr, *th_mod2 = nullptr;
     uint8_t* th_out = nullptr;
-    uint32_t ks_key = 0;       // kinds 10, 12: the key's index within the set
-    const uint8_t *th_g = nullptr, *th_y = nullptr;      // kind 11: the group's generator and the public value (th_nbytes each)
+    uint32_t ks_key = 0;       // the key's index within the set
+    const uint8_t *th_g = nullptr, *th_y = nullptr;
   };
   struct Batch {
     std::vector<Req*> reqs;
@@ -390,10 +412,10 @@ struct bftkv_gpu_batcher {
     (void)syscall(SYS_futex, reinterpret_cast<uint32_t*>(&lane_seq), FUTEX_WAKE_PRIVATE, 1, nullptr, nullptr, 0);
   }
 
-  // kinds 0 / 1: one staged device call per group, midstates instead of payloads; the (rare) items whose signatures ask for
+  // Collective, Signature: one staged device call per group, midstates instead of payloads; the (rare) items whose signatures ask for
   // another hash go through the ordinary entry point with their bytes afterwards
   void run_group(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
-    const int kind = g[0]->kind;
+    const Kind kind = g[0]->kind;
     const uint32_t n = (uint32_t)g.size();
     std::vector<StagedItem> items(n);
     for (uint32_t k = 0; k < n; ++k) {
@@ -402,7 +424,7 @@ struct bftkv_gpu_batcher {
     }
     std::vector<uint8_t> err(n), fenced(n), unres(n, 0);
     uint64_t a_ns = 0, d_ns = 0, l_ns = 0, s_ns = 0, n_to = 0;
-    const int rc = staged_group(lane.ctx, lane.pin, lane.pin_tb, lane.pin_sb, kind, g[0]->quorum, g[0]->has_cert, items, err.data(), fenced.data(),
+    const int rc = staged_group(lane.ctx, lane.pin, lane.pin_tb, lane.pin_sb, kind == Kind::Collective, g[0]->quorum, g[0]->has_cert, items, err.data(), fenced.data(),
                                 Req::failing(kind), &device_calls, &a_ns, &d_ns, &l_ns, &s_ns, &n_to, unres.data());
     ns_assemble.fetch_add(a_ns, std::memory_order_relaxed); ns_device.fetch_add(d_ns, std::memory_order_relaxed);
     ns_launch.fetch_add(l_ns, std::memory_order_relaxed); ns_spin.fetch_add(s_ns, std::memory_order_relaxed);
@@ -417,7 +439,7 @@ struct bftkv_gpu_batcher {
     std::vector<uint64_t> to{0};
     for (Req* r : g) to.push_back(to.back() + r->tbs_len);
     const size_t n = g.size();
-    std::vector<uint8_t> err(n, Req::failing(2));
+    std::vector<uint8_t> err(n, Req::failing(Kind::Message));
     int rc = 0;
     if (!lane.pin_tb.ensure(to.back() + 1)) rc = BFTKV_E_NOMEM;
     std::vector<uint64_t> signer(n), peer(n), poff(n + 1);
@@ -437,11 +459,11 @@ struct bftkv_gpu_batcher {
         else if (r->plain_out) r->rc = BFTKV_E_NOMEM;
         if (r->fname_out) copy_out(r->fname_out, fn.data() + k * 256, fl[k]);
       }
-      r->err = rc ? Req::failing(2) : err[k];
+      r->err = rc ? Req::failing(Kind::Message) : err[k];
     }
   }
 
-  // kind 3: certificates are registered on the ROOT context (the key table changes; the lanes' calls in flight drain first),
+  // Cert: certificates are registered on the ROOT context (the key table changes; the lanes' calls in flight drain first),
   // ReadEntity verdicts are remembered by certificate bytes, and the signatures of the group are verified in one device call
   void run_certs(std::vector<Req*>& g, uint64_t& device_calls) {
     std::vector<CertSigReq> reqs;
@@ -452,7 +474,7 @@ struct bftkv_gpu_batcher {
     for (size_t k = 0; k < g.size(); ++k) {
       Req* r = g[k];
       r->rc = rc;
-      r->err = Req::failing(3); r->fenced = 0;
+      r->err = Req::failing(Kind::Cert); r->fenced = 0;
       if (rc) continue;
       r->issuer_id = res[k].issuer_id;
       if (res[k].err == BFTKV_HOST_ERR_FENCED) r->fenced = 1;     // (the status byte stays a failure)
@@ -460,44 +482,56 @@ struct bftkv_gpu_batcher {
     }
   }
 
-  // kinds 4..7: the group's operations in ONE call of the batched entry point on the lane's context (threshold_capi.inc).  The
-  // distinct moduli of the group go into the call's modulus table in BYTE ORDER, so that the same set of moduli -- a protocol
-  // instance combines under the same few CA keys call after call -- finds its Montgomery tables in the context's cache.
-  // kind 8: ECDSA CalculateR.  A group's callers share one recognised curve (its bit size is part of the shape), which the
-  // call takes by value (th_mod = P || N || B || Gx || Gy, th_nbytes = fbytes, th_qbytes = bit size)
-  void run_ecdsa(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
-    const Req& r0 = *g[0];
-    const uint32_t n = (uint32_t)g.size(), k = r0.th_k, f = r0.th_nbytes;
-    const size_t rw = (size_t)k * (1 + 2 * f), vw = (size_t)k * f;
-    std::vector<uint8_t> ri((size_t)n * rw), vi((size_t)n * vw), out((size_t)n * f), st((size_t)n + 8, BFTKV_TH_FAILED);
-    std::vector<int32_t> xs((size_t)n * k);
-    for (uint32_t i = 0; i < n; ++i) {
-      memcpy(&ri[(size_t)i * rw], g[i]->th_a, rw);
-      memcpy(&vi[(size_t)i * vw], g[i]->th_b, vw);
-      memcpy(&xs[(size_t)i * k], g[i]->th_xs, (size_t)k * 4);
-    }
-    const int rc = ecdsa_calculate_r_impl(lane.ctx, n, k, xs.data(), ri.data(), vi.data(), r0.th_mod, r0.th_qbytes, out.data(), st.data(), false);
-    ++device_calls;
-    for (uint32_t i = 0; i < n; ++i) {
+  // one field of every request of a group, w bytes each, as one array
+  static std::vector<uint8_t> gather(const std::vector<Req*>& g, const uint8_t* Req::*field, size_t w) {
+    std::vector<uint8_t> v(g.size() * w);
+    if (w) for (size_t i = 0; i < g.size(); ++i) memcpy(&v[i * w], g[i]->*field, w);
+    return v;
+  }
+
+  // One publish path per result shape.
+  // status + verdict byte (the four verify kinds)
+  static void publish_verdicts(std::vector<Req*>& g, int rc, const uint8_t* st, const uint8_t* valid) {
+    for (size_t i = 0; i < g.size(); ++i) {
       Req* r = g[i];
       r->rc = rc;
-      r->err = rc ? Req::failing(8) : st[i];
-      if (!rc && st[i] == 0) memcpy(r->th_out, &out[(size_t)i * f], f);
+      r->err = rc ? Req::failing(r->kind) : st[i];
+      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
+    }
+  }
+  // status + o_w output bytes (the combines and both CalculateR); a failed operation leaves the caller's zeroes
+  static void publish_outputs(std::vector<Req*>& g, int rc, const uint8_t* st, const uint8_t* out, size_t o_w) {
+    for (size_t i = 0; i < g.size(); ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(r->kind) : st[i];
+      if (!rc && st[i] == 0) memcpy(r->th_out, out + i * o_w, o_w);
     }
   }
 
-  // kind 9: ECDSA verification.  A group's callers share a curve and a digest length (th_k = dlen); th_a = digest, th_b = r || s,
-  // th_mod2 = the key, th_out = the verdict byte.  The distinct keys of the group make the call's key table.
+  // EcdsaCalculateR
+  void run_ecdsa(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), k = r0.th_k, f = r0.th_nbytes;
+    const std::vector<uint8_t> ri = gather(g, &Req::th_a, (size_t)k * (1 + 2 * f)), vi = gather(g, &Req::th_b, (size_t)k * f);
+    std::vector<uint8_t> out((size_t)n * f), st((size_t)n + 8, BFTKV_TH_FAILED);
+    std::vector<int32_t> xs((size_t)n * k);
+    for (uint32_t i = 0; i < n; ++i) memcpy(&xs[(size_t)i * k], g[i]->th_xs, (size_t)k * 4);
+    const int rc = ecdsa_calculate_r_impl(lane.ctx, n, k, xs.data(), ri.data(), vi.data(), r0.th_mod, r0.th_qbytes, out.data(), st.data(), false);
+    ++device_calls;
+    publish_outputs(g, rc, st.data(), out.data(), f);
+  }
+
+  // EcdsaVerify: the distinct keys of the group make the call's key table, in first-seen order.
   void run_ecdsa_verify(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k, f = r0.th_nbytes;
     const size_t kw = 1 + 2 * (size_t)f;
     std::map<std::string, uint32_t> slot;
-    std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * f), keys, valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    const std::vector<uint8_t> dg = gather(g, &Req::th_a, dlen), sg = gather(g, &Req::th_b, 2 * (size_t)f);
+    std::vector<uint8_t> keys, valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
     std::vector<uint32_t> idx(n);
     for (uint32_t i = 0; i < n; ++i) {
-      memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
-      memcpy(&sg[(size_t)i * 2 * f], g[i]->th_b, 2 * (size_t)f);
       auto ins = slot.emplace(std::string((const char*)g[i]->th_mod2, kw), (uint32_t)slot.size());
       if (ins.second) keys.insert(keys.end(), g[i]->th_mod2, g[i]->th_mod2 + kw);
       idx[i] = ins.first->second;
@@ -505,21 +539,17 @@ struct bftkv_gpu_batcher {
     const int rc = ecdsa_verify_impl(lane.ctx, n, dg.data(), dlen, sg.data(), idx.data(), (uint32_t)slot.size(), keys.data(), r0.th_mod, r0.th_qbytes,
                                      valid.data(), st.data(), false);
     ++device_calls;
-    for (uint32_t i = 0; i < n; ++i) {
-      Req* r = g[i];
-      r->rc = rc;
-      r->err = rc ? Req::failing(9) : st[i];
-      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
-    }
+    publish_verdicts(g, rc, st.data(), valid.data());
   }
 
-  // kind 10: ECDSA verification under a resident key set.  A group's callers share the set (Req::quorum: the lane is a fork and
-  // passes the handle through) and a digest length (th_k); th_a = digest, th_b = r || s, ks_key = the key's index in the set.  The
-  // lane holds its hold on the root's tables from the look at the set's curve to the end of the call, so the set cannot be
-  // replaced by one of another signature length in between.  2 f bytes of every caller's signature are copied with f taken from the
-  // set found NOW: a caller that retired the set while this request waited, and let a set of a wider curve take the handle, has
-  // broken the rule in include/bftkv_gpu.h (no destroy while calls naming the set are in flight) and the copy reads past its buffer.
-  void run_ecdsa_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+  // EcdsaVerifyKeyset, DsaVerifyKeyset.  sig_bytes(ctx, handle): the bytes of one r || s under the set, 0 if there is no such set;
+  // verify: the kind's batched impl.  The lane holds its hold on the root's tables from the look at the set to the end of the device
+  // call, so the set cannot be replaced by one of another signature length in between.  The signature bytes of every caller are
+  // copied with the length taken from the set found NOW: a caller that retired the set while this request waited, and let a wider set
+  // take the handle, has broken the rule in include/bftkv_gpu.h (no destroy while calls naming the set are in flight) and the copy
+  // reads past its buffer.
+  template <typename SigBytes, typename Verify>
+  void run_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls, SigBytes sig_bytes, Verify verify) {
     const Req& r0 = *g[0];
     const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k;
     std::vector<uint8_t> valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
@@ -527,34 +557,23 @@ struct bftkv_gpu_batcher {
     {
       ctx_lock lk(lane.ctx->mu);
       KtRead kr(lane.ctx);
-      const EcKeySet* ks = kr.rc ? nullptr : ec_keyset_find(lane.ctx, r0.quorum);
+      const size_t sw = kr.rc ? 0 : sig_bytes(lane.ctx, r0.quorum);
       if (kr.rc) rc = kr.rc;
-      else if (!ks) rc = BFTKV_E_INVALID;
+      else if (!sw) rc = BFTKV_E_INVALID;
       else {
-        const uint32_t f = (ks->bits + 7) / 8;
-        std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * f);
+        const std::vector<uint8_t> dg = gather(g, &Req::th_a, dlen), sg = gather(g, &Req::th_b, sw);
         std::vector<uint32_t> idx(n);
-        for (uint32_t i = 0; i < n; ++i) {
-          memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
-          memcpy(&sg[(size_t)i * 2 * f], g[i]->th_b, 2 * (size_t)f);
-          idx[i] = g[i]->ks_key;
-        }
-        rc = ecdsa_verify_keyset_impl(lane.ctx, r0.quorum, n, dg.data(), dlen, sg.data(), idx.data(), valid.data(), st.data(), false);
+        for (uint32_t i = 0; i < n; ++i) idx[i] = g[i]->ks_key;
+        rc = verify(lane.ctx, r0.quorum, n, dg.data(), dlen, sg.data(), idx.data(), valid.data(), st.data(), false);
         ++device_calls;
       }
     }
-    for (uint32_t i = 0; i < n; ++i) {
-      Req* r = g[i];
-      r->rc = rc;
-      r->err = rc ? Req::failing(10) : st[i];
-      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
-    }
+    publish_verdicts(g, rc, st.data(), valid.data());
   }
 
-  // kind 11: DSA verification.  A group's callers share the widths and the digest length (th_k = dlen, th_nbytes = pbytes,
-  // th_qbytes = qbytes), whatever their groups and keys; th_a = digest, th_b = r || s, th_mod = p, th_mod2 = q, th_out = the verdict
-  // byte.  The distinct (p, q, g) of the batch make the call's group table in byte order (the same groups find their Montgomery
-  // rows in the context's cache call after call), the distinct (group, y) its key table.
+  // DsaVerify: a group's callers share the widths and the digest length, whatever their groups and keys.  The distinct (p, q, g) of
+  // the batch make the call's group table in BYTE ORDER (the same groups find their Montgomery rows in the context's cache call after
+  // call), the distinct (group, y) its key table in first-seen order.
   void run_dsa_verify(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
     const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k, pb = r0.th_nbytes, qb = r0.th_qbytes;
@@ -575,11 +594,10 @@ struct bftkv_gpu_batcher {
       memcpy(&gs[(size_t)n_groups * pb], kv.first.data() + pb + qb, pb);
       ++n_groups;
     }
-    std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * qb), valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    const std::vector<uint8_t> dg = gather(g, &Req::th_a, dlen), sg = gather(g, &Req::th_b, 2 * (size_t)qb);
+    std::vector<uint8_t> valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
     std::vector<uint32_t> idx(n), kgrp;
     for (uint32_t i = 0; i < n; ++i) {
-      memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
-      memcpy(&sg[(size_t)i * 2 * qb], g[i]->th_b, 2 * (size_t)qb);
       const uint32_t gi = gslot[group_key(g[i])];
       std::string kk((const char*)&gi, 4);
       kk.append((const char*)g[i]->th_y, pb);
@@ -590,103 +608,57 @@ struct bftkv_gpu_batcher {
     const int rc = dsa_verify_impl(lane.ctx, n, dg.data(), dlen, sg.data(), qb, idx.data(), (uint32_t)kslot.size(), ys.data(), kgrp.data(), pb, n_groups,
                                    ps.data(), qs.data(), gs.data(), valid.data(), st.data(), false);
     ++device_calls;
-    for (uint32_t i = 0; i < n; ++i) {
-      Req* r = g[i];
-      r->rc = rc;
-      r->err = rc ? Req::failing(11) : st[i];
-      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
-    }
+    publish_verdicts(g, rc, st.data(), valid.data());
   }
 
-  // kind 12: DSA verification under a resident key set, as kind 10: a group's callers share the set (Req::quorum) and a digest length
-  // (th_k); th_a = digest, th_b = r || s, ks_key = the key's index in the set.  The lane holds the root's tables from the look at the
-  // set's qbytes to the end of the device call, so the set cannot be replaced by one of another signature length in between.
-  void run_dsa_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
-    const Req& r0 = *g[0];
-    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k;
-    std::vector<uint8_t> valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
-    int rc;
-    {
-      ctx_lock lk(lane.ctx->mu);
-      KtRead kr(lane.ctx);
-      const DsaKeySet* ks = kr.rc ? nullptr : dsa_keyset_find(lane.ctx, r0.quorum);
-      if (kr.rc) rc = kr.rc;
-      else if (!ks) rc = BFTKV_E_INVALID;
-      else {
-        const uint32_t qb = ks->qbytes;
-        std::vector<uint8_t> dg((size_t)n * dlen), sg((size_t)n * 2 * qb);
-        std::vector<uint32_t> idx(n);
-        for (uint32_t i = 0; i < n; ++i) {
-          memcpy(&dg[(size_t)i * dlen], g[i]->th_a, dlen);
-          memcpy(&sg[(size_t)i * 2 * qb], g[i]->th_b, 2 * (size_t)qb);
-          idx[i] = g[i]->ks_key;
-        }
-        rc = dsa_verify_keyset_impl(lane.ctx, r0.quorum, n, dg.data(), dlen, sg.data(), idx.data(), valid.data(), st.data(), false);
-        ++device_calls;
-      }
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-      Req* r = g[i];
-      r->rc = rc;
-      r->err = rc ? Req::failing(12) : st[i];
-      *r->th_out = !rc && st[i] == BFTKV_TH_OK ? valid[i] : 0;
-    }
-  }
-
+  // ModmulProduct, LagrangeCombine, DsaCalculateR, Modexp: the group's operations in ONE call of the batched entry point on the
+  // lane's context (threshold_capi.inc).  The distinct moduli of the group go into the call's modulus table in BYTE ORDER, so that the
+  // same set of moduli -- a protocol instance combines under the same few CA keys call after call -- finds its Montgomery tables in
+  // the context's cache.
   void run_threshold(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
     const Req& r0 = *g[0];
-    const int kind = r0.kind;
-    if (kind == 11) { run_dsa_verify(lane, g, device_calls); return; }
-    if (kind == 8) { run_ecdsa(lane, g, device_calls); return; }
-    if (kind == 9) { run_ecdsa_verify(lane, g, device_calls); return; }
-    if (kind == 10) { run_ecdsa_verify_keyset(lane, g, device_calls); return; }
-    if (kind == 12) { run_dsa_verify_keyset(lane, g, device_calls); return; }
+    const Kind kind = r0.kind;
+    const bool calc_r = kind == Kind::DsaCalculateR, modexp = kind == Kind::Modexp;
     const uint32_t n = (uint32_t)g.size(), k = r0.th_k, nb = r0.th_nbytes, qb = r0.th_qbytes;
-    // (CalculateR: a group (p, q) is one table row)
-    std::map<std::string, uint32_t> slot;
-    for (Req* r : g) {
+    auto mod_key = [&](const Req* r) {      // (CalculateR: a group (p, q) is one table row)
       std::string key((const char*)r->th_mod, nb);
-      if (kind == 6) key.append((const char*)r->th_mod2, qb);
-      slot.emplace(std::move(key), 0u);
-    }
+      if (calc_r) key.append((const char*)r->th_mod2, qb);
+      return key;
+    };
+    std::map<std::string, uint32_t> slot;
+    for (Req* r : g) slot.emplace(mod_key(r), 0u);
     uint32_t n_mods = 0;
-    std::vector<uint8_t> mods((size_t)slot.size() * nb), mods2(kind == 6 ? (size_t)slot.size() * qb : 0);
+    std::vector<uint8_t> mods((size_t)slot.size() * nb), mods2(calc_r ? (size_t)slot.size() * qb : 0);
     for (auto& kv : slot) {
       kv.second = n_mods;
       memcpy(&mods[(size_t)n_mods * nb], kv.first.data(), nb);
-      if (kind == 6) memcpy(&mods2[(size_t)n_mods * qb], kv.first.data() + nb, qb);
+      if (calc_r) memcpy(&mods2[(size_t)n_mods * qb], kv.first.data() + nb, qb);
       ++n_mods;
     }
     std::vector<uint32_t> idx(n);
-    const size_t a_w = (size_t)(kind == 7 ? 1 : k) * nb;                               // bytes of th_a per operation
-    const size_t b_w = kind == 6 ? (size_t)k * qb : kind == 7 ? (size_t)qb : 0;        // ... of th_b
-    const size_t o_w = kind == 6 ? qb : nb;
-    std::vector<uint8_t> a((size_t)n * a_w), b((size_t)n * b_w + 1), out((size_t)n * o_w), st((size_t)n + 8, 0);
-    std::vector<int32_t> xs(kind == 5 || kind == 6 ? (size_t)n * k : 0);
+    const size_t a_w = (size_t)(modexp ? 1 : k) * nb;                                  // bytes of th_a per operation
+    const size_t b_w = calc_r ? (size_t)k * qb : modexp ? (size_t)qb : 0;              // ... of th_b
+    const size_t o_w = calc_r ? qb : nb;
+    // (modmul_product_impl and modexp_impl write no status: the bytes start at 0 here, not at BFTKV_TH_FAILED)
+    const std::vector<uint8_t> a = gather(g, &Req::th_a, a_w), b = gather(g, &Req::th_b, b_w);
+    std::vector<uint8_t> out((size_t)n * o_w), st((size_t)n + 8, 0);
+    std::vector<int32_t> xs(kind == Kind::LagrangeCombine || calc_r ? (size_t)n * k : 0);
     for (uint32_t i = 0; i < n; ++i) {
-      const Req* r = g[i];
-      std::string key((const char*)r->th_mod, nb);
-      if (kind == 6) key.append((const char*)r->th_mod2, qb);
-      idx[i] = slot[key];
-      memcpy(&a[(size_t)i * a_w], r->th_a, a_w);
-      if (b_w) memcpy(&b[(size_t)i * b_w], r->th_b, b_w);
-      if (!xs.empty()) memcpy(&xs[(size_t)i * k], r->th_xs, (size_t)k * 4);
+      idx[i] = slot[mod_key(g[i])];
+      if (!xs.empty()) memcpy(&xs[(size_t)i * k], g[i]->th_xs, (size_t)k * 4);
     }
     int rc;
     switch (kind) {
-      case 4: rc = modmul_product_impl(lane.ctx, n, k, a.data(), nb, idx.data(), n_mods, mods.data(), out.data(), false); break;
-      case 5: rc = lagrange_combine_impl(lane.ctx, n, k, xs.data(), a.data(), nb, idx.data(), n_mods, mods.data(), out.data(), st.data(), false); break;
-      case 6: rc = dsa_calculate_r_impl(lane.ctx, n, k, xs.data(), a.data(), nb, b.data(), qb, idx.data(), n_mods, mods.data(), mods2.data(), out.data(),
-                                        st.data(), false); break;
+      case Kind::ModmulProduct: rc = modmul_product_impl(lane.ctx, n, k, a.data(), nb, idx.data(), n_mods, mods.data(), out.data(), false); break;
+      case Kind::LagrangeCombine:
+        rc = lagrange_combine_impl(lane.ctx, n, k, xs.data(), a.data(), nb, idx.data(), n_mods, mods.data(), out.data(), st.data(), false); break;
+      case Kind::DsaCalculateR:
+        rc = dsa_calculate_r_impl(lane.ctx, n, k, xs.data(), a.data(), nb, b.data(), qb, idx.data(), n_mods, mods.data(), mods2.data(), out.data(),
+                                  st.data(), false); break;
       default: rc = modexp_impl(lane.ctx, n, a.data(), nb, idx.data(), n_mods, mods.data(), b.data(), qb, true, out.data()); break;
     }
     ++device_calls;
-    for (uint32_t i = 0; i < n; ++i) {
-      Req* r = g[i];
-      r->rc = rc;
-      r->err = rc ? Req::failing(kind) : st[i];
-      if (!rc && st[i] == 0) memcpy(r->th_out, &out[(size_t)i * o_w], o_w);      // (a failed operation leaves the caller's zeroes)
-    }
+    publish_outputs(g, rc, st.data(), out.data(), o_w);
   }
 
   // group by (kind, quorum / certificate use, threshold shape): one device call per group
@@ -701,9 +673,27 @@ struct bftkv_gpu_batcher {
             batch[j]->th_shape == batch[i]->th_shape) {
           g.push_back(batch[j]); taken[j] = true;
         }
-      if (g[0]->kind >= 4) run_threshold(lane, g, calls);
-      else if (g[0]->kind == 3) run_certs(g, calls);
-      else if (g[0]->kind == 2) run_messages(lane, g, calls); else run_group(lane, g, calls);
+      switch (g[0]->kind) {
+        case Kind::Collective: case Kind::Signature: run_group(lane, g, calls); break;
+        case Kind::Message: run_messages(lane, g, calls); break;
+        case Kind::Cert: run_certs(g, calls); break;
+        case Kind::ModmulProduct: case Kind::LagrangeCombine: case Kind::DsaCalculateR: case Kind::Modexp: run_threshold(lane, g, calls); break;
+        case Kind::EcdsaCalculateR: run_ecdsa(lane, g, calls); break;
+        case Kind::EcdsaVerify: run_ecdsa_verify(lane, g, calls); break;
+        case Kind::EcdsaVerifyKeyset:
+          run_verify_keyset(lane, g, calls, [](const bftkv_gpu_ctx* c, int set) {
+            const EcKeySet* ks = ec_keyset_find(c, set);
+            return ks ? 2 * (size_t)((ks->bits + 7) / 8) : 0;
+          }, ecdsa_verify_keyset_impl);
+          break;
+        case Kind::DsaVerify: run_dsa_verify(lane, g, calls); break;
+        case Kind::DsaVerifyKeyset:
+          run_verify_keyset(lane, g, calls, [](const bftkv_gpu_ctx* c, int set) {
+            const DsaKeySet* ks = dsa_keyset_find(c, set);
+            return ks ? 2 * (size_t)ks->qbytes : 0;
+          }, dsa_verify_keyset_impl);
+          break;
+      }
     }
     return calls;
   }
@@ -715,8 +705,8 @@ struct bftkv_gpu_batcher {
     // STARTS after destroy() has returned is the caller's bug, as with any destroyed handle.)
     inside.fetch_add(1);
     if (stop.load()) { inside.fetch_sub(1); return BFTKV_E_STATE; }
-    // the caller's own thread walks its payload's hash chain (kinds 0 / 1; a message's signed bytes are found by the framing)
-    if (r.kind < 2) {
+    // the caller's own thread walks its payload's hash chain (a message's signed bytes are found by the framing)
+    if (hashed_by_caller(r.kind)) {
       const uint64_t t_h = now_ns();
       hostsha::midstate(r.tbs, r.tbs_len, r.mid);
       ns_hash.fetch_add(now_ns() - t_h, std::memory_order_relaxed);
@@ -765,6 +755,8 @@ struct bftkv_gpu_batcher {
   }
 };
 
+using BatcherKind = bftkv_gpu_batcher::Kind;
+
 extern "C" {
 
 bftkv_gpu_batcher* bftkv_gpu_batcher_create_lanes(bftkv_gpu_ctx* ctx, uint32_t max_items, uint32_t max_wait_us, uint32_t n_lanes) {
@@ -810,7 +802,7 @@ int bftkv_gpu_batcher_collective_verify(bftkv_gpu_batcher* b, int quorum, const 
   if (err_out) *err_out = BFTKV_ERR_INSUFFICIENT_SIGNATURES;
   if (fenced_out) *fenced_out = 0;
   if (!b || !err_out || (!tbs && tbs_len) || (!ss && ss_len)) return BFTKV_E_INVALID;
-  bftkv_gpu_batcher::Req r{0, quorum, tbs, tbs_len, ss, ss_len, false, 0};
+  bftkv_gpu_batcher::Req r{BatcherKind::Collective, quorum, tbs, tbs_len, ss, ss_len, false, 0};
   int rc = b->submit(r);
   *err_out = rc ? (uint8_t)BFTKV_ERR_INSUFFICIENT_SIGNATURES : r.err;
   if (fenced_out) *fenced_out = r.fenced;
@@ -822,7 +814,7 @@ int bftkv_gpu_batcher_signature_verify(bftkv_gpu_batcher* b, const uint8_t* tbs,
   if (err_out) *err_out = BFTKV_ERR_INVALID_SIGNATURE;
   if (fenced_out) *fenced_out = 0;
   if (!b || !err_out || (!tbs && tbs_len) || (!sig && sig_len)) return BFTKV_E_INVALID;
-  bftkv_gpu_batcher::Req r{1, -1, tbs, tbs_len, sig, sig_len, cert_key_id != nullptr, cert_key_id ? *cert_key_id : 0};
+  bftkv_gpu_batcher::Req r{BatcherKind::Signature, bftkv_gpu_batcher::NO_QUORUM, tbs, tbs_len, sig, sig_len, cert_key_id != nullptr, cert_key_id ? *cert_key_id : 0};
   int rc = b->submit(r);
   *err_out = rc ? (uint8_t)BFTKV_ERR_INVALID_SIGNATURE : r.err;
   if (fenced_out) *fenced_out = r.fenced;
@@ -860,7 +852,7 @@ int bftkv_gpu_batcher_cert_verify(bftkv_gpu_batcher* b, const uint8_t* cert, uin
       return 0;
     }
     if (known && sig_len) {
-      bftkv_gpu_batcher::Req f{1, -1, tbs ? tbs : &empty, tbs_len, sig, sig_len, true, cf.issuer_id};
+      bftkv_gpu_batcher::Req f{BatcherKind::Signature, bftkv_gpu_batcher::NO_QUORUM, tbs ? tbs : &empty, tbs_len, sig, sig_len, true, cf.issuer_id};
       f.cert_group = cf.group; f.cert_epoch = cf.epoch;
       const int frc = b->submit(f);
       if (!frc && !f.unresolved && !f.fenced) {
@@ -874,7 +866,7 @@ int bftkv_gpu_batcher_cert_verify(bftkv_gpu_batcher* b, const uint8_t* cert, uin
       b->n_calls.fetch_sub(1, std::memory_order_relaxed);     // (served once: by the call below)
     }
   }
-  bftkv_gpu_batcher::Req r{3, -3, tbs ? tbs : &empty, tbs_len, sig, sig_len, false, 0};
+  bftkv_gpu_batcher::Req r{BatcherKind::Cert, bftkv_gpu_batcher::NO_QUORUM, tbs ? tbs : &empty, tbs_len, sig, sig_len, false, 0};
   r.cert = cert; r.cert_len = cert_len;
   int rc = b->submit(r);
   *err_out = rc ? (uint8_t)BFTKV_ERR_INVALID_SIGNATURE : r.err;
@@ -919,7 +911,7 @@ int bftkv_gpu_batcher_message_verify(bftkv_gpu_batcher* b, const uint8_t* msg, u
                                      uint8_t* fname_len_out) {
   if (status_out) *status_out = BFTKV_MSG_READ_ERROR;
   if (!b || !status_out) return BFTKV_E_INVALID;
-  bftkv_gpu_batcher::Req r{2, -2, msg, msg_len, nullptr, 0, false, 0};
+  bftkv_gpu_batcher::Req r{BatcherKind::Message, bftkv_gpu_batcher::NO_QUORUM, msg, msg_len, nullptr, 0, false, 0};
   r.plain_out = plain_out; r.plain_cap = plain_cap; r.fname_out = fname_out;
   int rc = b->submit(r);
   *status_out = rc ? (uint8_t)BFTKV_MSG_READ_ERROR : r.err;
@@ -931,42 +923,59 @@ int bftkv_gpu_batcher_message_verify(bftkv_gpu_batcher* b, const uint8_t* msg, u
 }
 
 // ---- one threshold share-combine operation per call (BASELINE config 5 behind the reference's seam) ----
-static int threshold_submit(bftkv_gpu_batcher* b, int kind, uint32_t k, const int32_t* xs, const uint8_t* a, uint32_t nbytes, const uint8_t* bb,
-                            uint32_t qbytes, const uint8_t* mod, const uint8_t* mod2, uint8_t* out, uint32_t out_bytes, uint8_t* status_out) {
-  if (status_out) *status_out = BFTKV_TH_FAILED;
-  if (out && out_bytes && out_bytes <= 256) memset(out, 0, out_bytes);
-  if (!b || !status_out || !out || !a || !mod || nbytes == 0 || nbytes > 256 || k == 0 || k > 1024) return BFTKV_E_INVALID;
-  if ((kind == 5 || kind == 6) && !xs) return BFTKV_E_INVALID;
-  if (kind == 6 && (!bb || !mod2 || qbytes == 0 || qbytes > 32)) return BFTKV_E_INVALID;
-  if (kind == 7 && (!bb || qbytes == 0 || qbytes > 1024)) return BFTKV_E_INVALID;
-  // what the batched entry points refuse for the WHOLE call is refused here for this caller alone: an even or over-wide
-  // modulus must not fail the strangers it shares a device call with
-  if (!(mod[nbytes - 1] & 1) || (kind == 6 && !(mod2[qbytes - 1] & 1))) return BFTKV_E_UNSUPPORTED;
-  if (hostbn::bit_length(mod, nbytes) > 2048 || hostbn::bit_length(mod, nbytes) < 2) return BFTKV_E_UNSUPPORTED;
-  if (kind == 6 && hostbn::bit_length(mod2, qbytes) < 2) return BFTKV_E_UNSUPPORTED;
-  bftkv_gpu_batcher::Req r{kind, -4, nullptr, 0, nullptr, 0, false, 0};
-  r.th_shape = (uint64_t)kind | (uint64_t)k << 8 | (uint64_t)nbytes << 24 | (uint64_t)qbytes << 40;
-  r.th_k = k; r.th_nbytes = nbytes; r.th_qbytes = qbytes; r.th_xs = xs; r.th_a = a; r.th_b = bb; r.th_mod = mod; r.th_mod2 = mod2; r.th_out = out;
+// a threshold-style request with its shape, about to be filled in by its entry point
+static bftkv_gpu_batcher::Req threshold_req(BatcherKind kind, int quorum, uint64_t a, uint64_t b = 0, uint64_t c = 0) {
+  bftkv_gpu_batcher::Req r{kind, quorum, nullptr, 0, nullptr, 0, false, 0};
+  r.th_shape = bftkv_gpu_batcher::Req::shape(kind, a, b, c);
+  return r;
+}
+// submit, fail closed: the status byte is the request's only when the call succeeded
+static int threshold_submit(bftkv_gpu_batcher* b, bftkv_gpu_batcher::Req& r, uint8_t* status_out) {
   const int rc = b->submit(r);
   *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
   return rc;
 }
+// ... and so is the verdict (th_out), for the four verify kinds
+static int verdict_submit(bftkv_gpu_batcher* b, bftkv_gpu_batcher::Req& r, uint8_t* status_out) {
+  const int rc = threshold_submit(b, r, status_out);
+  if (rc) *r.th_out = 0;
+  return rc;
+}
+
+static int combine_submit(bftkv_gpu_batcher* b, BatcherKind kind, uint32_t k, const int32_t* xs, const uint8_t* a, uint32_t nbytes, const uint8_t* bb,
+                          uint32_t qbytes, const uint8_t* mod, const uint8_t* mod2, uint8_t* out, uint32_t out_bytes, uint8_t* status_out) {
+  const bool calc_r = kind == BatcherKind::DsaCalculateR;
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (out && out_bytes && out_bytes <= 256) memset(out, 0, out_bytes);
+  if (!b || !status_out || !out || !a || !mod || nbytes == 0 || nbytes > 256 || k == 0 || k > 1024) return BFTKV_E_INVALID;
+  if ((kind == BatcherKind::LagrangeCombine || calc_r) && !xs) return BFTKV_E_INVALID;
+  if (calc_r && (!bb || !mod2 || qbytes == 0 || qbytes > 32)) return BFTKV_E_INVALID;
+  if (kind == BatcherKind::Modexp && (!bb || qbytes == 0 || qbytes > 1024)) return BFTKV_E_INVALID;
+  // what the batched entry points refuse for the WHOLE call is refused here for this caller alone: an even or over-wide
+  // modulus must not fail the strangers it shares a device call with
+  if (!(mod[nbytes - 1] & 1) || (calc_r && !(mod2[qbytes - 1] & 1))) return BFTKV_E_UNSUPPORTED;
+  if (hostbn::bit_length(mod, nbytes) > 2048 || hostbn::bit_length(mod, nbytes) < 2) return BFTKV_E_UNSUPPORTED;
+  if (calc_r && hostbn::bit_length(mod2, qbytes) < 2) return BFTKV_E_UNSUPPORTED;
+  bftkv_gpu_batcher::Req r = threshold_req(kind, bftkv_gpu_batcher::NO_QUORUM, k, nbytes, qbytes);
+  r.th_k = k; r.th_nbytes = nbytes; r.th_qbytes = qbytes; r.th_xs = xs; r.th_a = a; r.th_b = bb; r.th_mod = mod; r.th_mod2 = mod2; r.th_out = out;
+  return threshold_submit(b, r, status_out);
+}
 
 int bftkv_gpu_batcher_modmul_product(bftkv_gpu_batcher* b, uint32_t k, const uint8_t* factors, uint32_t nbytes, const uint8_t* mod, uint8_t* out,
                                      uint8_t* status_out) {
-  return threshold_submit(b, 4, k, nullptr, factors, nbytes, nullptr, 0, mod, nullptr, out, nbytes, status_out);
+  return combine_submit(b, BatcherKind::ModmulProduct, k, nullptr, factors, nbytes, nullptr, 0, mod, nullptr, out, nbytes, status_out);
 }
 int bftkv_gpu_batcher_lagrange_combine(bftkv_gpu_batcher* b, uint32_t k, const int32_t* xs, const uint8_t* ys, uint32_t nbytes, const uint8_t* mod,
                                        uint8_t* out, uint8_t* status_out) {
-  return threshold_submit(b, 5, k, xs, ys, nbytes, nullptr, 0, mod, nullptr, out, nbytes, status_out);
+  return combine_submit(b, BatcherKind::LagrangeCombine, k, xs, ys, nbytes, nullptr, 0, mod, nullptr, out, nbytes, status_out);
 }
 int bftkv_gpu_batcher_dsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const int32_t* xs, const uint8_t* ri, uint32_t pbytes, const uint8_t* vi,
                                       uint32_t qbytes, const uint8_t* p, const uint8_t* q, uint8_t* r_out, uint8_t* status_out) {
-  return threshold_submit(b, 6, k, xs, ri, pbytes, vi, qbytes, p, q, r_out, qbytes, status_out);
+  return combine_submit(b, BatcherKind::DsaCalculateR, k, xs, ri, pbytes, vi, qbytes, p, q, r_out, qbytes, status_out);
 }
 int bftkv_gpu_batcher_modexp(bftkv_gpu_batcher* b, const uint8_t* base, uint32_t nbytes, const uint8_t* exp, uint32_t exp_len, const uint8_t* mod,
                              uint8_t* out, uint8_t* status_out) {
-  return threshold_submit(b, 7, 1, nullptr, base, nbytes, exp, exp_len, mod, nullptr, out, nbytes, status_out);
+  return combine_submit(b, BatcherKind::Modexp, 1, nullptr, base, nbytes, exp, exp_len, mod, nullptr, out, nbytes, status_out);
 }
 
 int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
@@ -977,12 +986,9 @@ int bftkv_gpu_batcher_ecdsa_calculate_r(bftkv_gpu_batcher* b, uint32_t k, const 
   if (!b || !status_out || !r_out || !xs || !ri || !vi || !curve || bit_size == 0 || bit_size > 521 || k == 0 || k > 1024) return BFTKV_E_INVALID;
   // refused for this caller alone, as an unsupported modulus is on the other threshold entries
   if (ec_curve_id(curve, bit_size) < 0) return BFTKV_E_UNSUPPORTED;
-  bftkv_gpu_batcher::Req r{8, -4, nullptr, 0, nullptr, 0, false, 0};
-  r.th_shape = (uint64_t)8 | (uint64_t)k << 8 | (uint64_t)bit_size << 24;
-  r.th_k = k; r.th_nbytes = f; r.th_qbytes = bit_size; r.th_xs = xs; r.th_a = ri; r.th_b = vi; r.th_mod = curve; r.th_mod2 = nullptr; r.th_out = r_out;
-  const int rc = b->submit(r);
-  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
-  return rc;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::EcdsaCalculateR, bftkv_gpu_batcher::NO_QUORUM, k, bit_size);
+  r.th_k = k; r.th_nbytes = f; r.th_qbytes = bit_size; r.th_xs = xs; r.th_a = ri; r.th_b = vi; r.th_mod = curve; r.th_out = r_out;
+  return threshold_submit(b, r, status_out);
 }
 
 int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, const uint8_t* key,
@@ -992,28 +998,29 @@ int bftkv_gpu_batcher_ecdsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, 
   if (!b || !status_out || !valid_out || !digest || !sig || !key || !curve || bit_size == 0 || bit_size > 521 || dlen == 0 || dlen > 66)
     return BFTKV_E_INVALID;
   if (ec_curve_id(curve, bit_size) < 0) return BFTKV_E_UNSUPPORTED;       // for this caller alone
-  bftkv_gpu_batcher::Req r{9, -4, nullptr, 0, nullptr, 0, false, 0};
-  r.th_shape = (uint64_t)9 | (uint64_t)dlen << 8 | (uint64_t)bit_size << 24;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::EcdsaVerify, bftkv_gpu_batcher::NO_QUORUM, dlen, bit_size);
   r.th_k = dlen; r.th_nbytes = (bit_size + 7) / 8; r.th_qbytes = bit_size; r.th_a = digest; r.th_b = sig; r.th_mod = curve; r.th_mod2 = key;
   r.th_out = valid_out;
-  const int rc = b->submit(r);
-  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
-  if (rc) *valid_out = 0;
-  return rc;
+  return verdict_submit(b, r, status_out);
 }
 
-int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen, const uint8_t* sig,
-                                          uint8_t* valid_out, uint8_t* status_out) {
+// one signature under key `key` of a resident set (an unknown handle fails its own group alone)
+static int keyset_submit(bftkv_gpu_batcher* b, BatcherKind kind, uint32_t max_dlen, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen,
+                         const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out) {
   if (status_out) *status_out = BFTKV_TH_FAILED;
   if (valid_out) *valid_out = 0;
-  if (!b || !status_out || !valid_out || !digest || !sig || dlen == 0 || dlen > 66) return BFTKV_E_INVALID;
-  bftkv_gpu_batcher::Req r{10, keyset, nullptr, 0, nullptr, 0, false, 0};       // (an unknown handle fails its own group alone)
-  r.th_shape = (uint64_t)10 | (uint64_t)dlen << 8;
+  if (!b || !status_out || !valid_out || !digest || !sig || dlen == 0 || dlen > max_dlen) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r = threshold_req(kind, keyset, dlen);
   r.th_k = dlen; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
-  const int rc = b->submit(r);
-  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
-  if (rc) *valid_out = 0;
-  return rc;
+  return verdict_submit(b, r, status_out);
+}
+int bftkv_gpu_batcher_ecdsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen, const uint8_t* sig,
+                                          uint8_t* valid_out, uint8_t* status_out) {
+  return keyset_submit(b, BatcherKind::EcdsaVerifyKeyset, 66, keyset, key, digest, dlen, sig, valid_out, status_out);
+}
+int bftkv_gpu_batcher_dsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen, const uint8_t* sig,
+                                        uint8_t* valid_out, uint8_t* status_out) {
+  return keyset_submit(b, BatcherKind::DsaVerifyKeyset, 64, keyset, key, digest, dlen, sig, valid_out, status_out);
 }
 
 int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t dlen, const uint8_t* sig, uint32_t qbytes, const uint8_t* y,
@@ -1025,28 +1032,10 @@ int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, ui
     return BFTKV_E_INVALID;
   // what the batched entry refuses for the WHOLE call is refused here for this caller alone
   if (!(p[pbytes - 1] & 1) || !(q[qbytes - 1] & 1)) return BFTKV_E_UNSUPPORTED;
-  bftkv_gpu_batcher::Req r{11, -4, nullptr, 0, nullptr, 0, false, 0};
-  r.th_shape = (uint64_t)11 | (uint64_t)dlen << 8 | (uint64_t)pbytes << 24 | (uint64_t)qbytes << 40;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::DsaVerify, bftkv_gpu_batcher::NO_QUORUM, dlen, pbytes, qbytes);
   r.th_k = dlen; r.th_nbytes = pbytes; r.th_qbytes = qbytes; r.th_a = digest; r.th_b = sig; r.th_mod = p; r.th_mod2 = q; r.th_g = g; r.th_y = y;
   r.th_out = valid_out;
-  const int rc = b->submit(r);
-  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
-  if (rc) *valid_out = 0;
-  return rc;
-}
-
-int bftkv_gpu_batcher_dsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen, const uint8_t* sig,
-                                        uint8_t* valid_out, uint8_t* status_out) {
-  if (status_out) *status_out = BFTKV_TH_FAILED;
-  if (valid_out) *valid_out = 0;
-  if (!b || !status_out || !valid_out || !digest || !sig || dlen == 0 || dlen > 64) return BFTKV_E_INVALID;
-  bftkv_gpu_batcher::Req r{12, keyset, nullptr, 0, nullptr, 0, false, 0};       // (an unknown handle fails its own group alone)
-  r.th_shape = (uint64_t)12 | (uint64_t)dlen << 8;
-  r.th_k = dlen; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
-  const int rc = b->submit(r);
-  *status_out = rc ? (uint8_t)BFTKV_TH_FAILED : r.err;
-  if (rc) *valid_out = 0;
-  return rc;
+  return verdict_submit(b, r, status_out);
 }
 
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]) {
@@ -1057,11 +1046,11 @@ int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]) {
 
 // The staged route for callers that hold a small batch themselves: payload chains hashed on the calling thread, one pinned
 // buffer in, results through mapped host memory (what a batcher's leader does for its batch).
-static int small_verify(bftkv_gpu_ctx* c, int kind, int quorum, uint32_t n, const uint8_t* tbs, const uint64_t* tbs_off, const uint8_t* ss,
+static int small_verify(bftkv_gpu_ctx* c, bool collective, int quorum, uint32_t n, const uint8_t* tbs, const uint64_t* tbs_off, const uint8_t* ss,
                         const uint64_t* ss_off, const uint64_t* cert_key_id, uint8_t* err_out, uint8_t* fenced_out) {
   if (!c || (n && (!tbs_off || !ss_off || !err_out))) return BFTKV_E_INVALID;
   if (n == 0) return 0;
-  const uint8_t failing = kind == 0 ? BFTKV_ERR_INSUFFICIENT_SIGNATURES : BFTKV_ERR_INVALID_SIGNATURE;
+  const uint8_t failing = collective ? BFTKV_ERR_INSUFFICIENT_SIGNATURES : BFTKV_ERR_INVALID_SIGNATURE;
   for (uint32_t i = 0; i < n; ++i) { err_out[i] = failing; if (fenced_out) fenced_out[i] = 0; }
   int rco;
   if ((rco = check_offsets(c, tbs_off, n, "tbs_off not monotone from 0")) || (rco = check_offsets(c, ss_off, n, "ss_off not monotone from 0"))) return rco;
@@ -1078,19 +1067,19 @@ static int small_verify(bftkv_gpu_ctx* c, int kind, int quorum, uint32_t n, cons
   ctx_lock lk(c->mu);      // the context's staging buffers
   if (!c->small_pin) c->small_pin = new PinnedBuf[3];
   PinnedBuf* pb = (PinnedBuf*)c->small_pin;
-  const int rc = staged_group(c, pb[0], pb[1], pb[2], kind, quorum, cert_key_id != nullptr, items, err_out, fenced.data(), failing, &calls);
+  const int rc = staged_group(c, pb[0], pb[1], pb[2], collective, quorum, cert_key_id != nullptr, items, err_out, fenced.data(), failing, &calls);
   if (fenced_out) copy_out(fenced_out, fenced.data(), n);
   return rc;
 }
 
 int bftkv_gpu_collective_verify_small(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off, const uint8_t* ss,
                                       const uint64_t* ss_off, uint8_t* err_out, uint8_t* fenced_out) {
-  return small_verify(c, 0, quorum, n_items, tbs, tbs_off, ss, ss_off, nullptr, err_out, fenced_out);
+  return small_verify(c, true, quorum, n_items, tbs, tbs_off, ss, ss_off, nullptr, err_out, fenced_out);
 }
 
 int bftkv_gpu_signature_verify_small(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off, const uint8_t* sig,
                                      const uint64_t* sig_off, const uint64_t* cert_key_id, uint8_t* err_out, uint8_t* fenced_out) {
-  return small_verify(c, 1, -1, n_items, tbs, tbs_off, sig, sig_off, cert_key_id, err_out, fenced_out);
+  return small_verify(c, false, -1, n_items, tbs, tbs_off, sig, sig_off, cert_key_id, err_out, fenced_out);
 }
 
 int bftkv_gpu_batcher_times(bftkv_gpu_batcher* b, uint64_t ns[8]) {

@@ -116,6 +116,7 @@ struct DsaKeySet {
   DevBuf modp[3], modq[3];                 // n, R^2, -n^-1 rows of every p and q (the set's own copies: no call uploads anything)
   DevBuf q_be, key_group;                  // [n_groups][qbytes] bytes; [n_keys] clamped group indices
   uint64_t table_bytes() const { return (uint64_t)(n_groups + n_keys) * windows * ((1u << w) - 1u) * MONT_N * 4; }
+  static ModTab rows(const DevBuf (&m)[3]) { return ModTab{m[0].as<uint32_t>(), m[1].as<uint32_t>(), m[2].as<uint32_t>(), nullptr}; }      // rows(modp), rows(modq)
   void release() { tab.release(); q_be.release(); key_group.release(); for (DevBuf& b : modp) b.release(); for (DevBuf& b : modq) b.release(); }
 };
 

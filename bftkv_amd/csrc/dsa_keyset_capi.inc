@@ -33,9 +33,8 @@ int dsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* key
   auto build = [&]() -> int {
     ks.n_keys = n_keys; ks.n_groups = n_groups; ks.pbytes = pbytes; ks.qbytes = qbytes;
     ks.w = window_bits ? window_bits : DSAV_COMB_WDEF;
-    uint32_t max_qbits = 1;
-    for (uint32_t i = 0; i < n_groups; ++i) max_qbits = std::max(max_qbits, (uint32_t)hostbn::bit_length(q + (size_t)i * qbytes, qbytes));
-    ks.windows = dsav_comb_windows(max_qbits, ks.w);
+    const DsaBases hb(n_keys, keys_y, key_group, pbytes, n_groups, q, qbytes, g);
+    ks.windows = dsav_comb_windows(hb.max_qbits, ks.w);
     // the rows of every p and q, copied out of the context's cache (which may drop them) into the set
     ModTab mp, mq;
     if ((rc = make_modtab(c, sb, p, n_groups, pbytes, &mp))) return rc;          // (an even p or q: BFTKV_E_UNSUPPORTED, no set)
@@ -48,24 +47,18 @@ int dsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* key
       HIPCHK(c, hipMemcpyAsync(ks.modp[k].p, srcp[k], len[k], hipMemcpyDeviceToDevice, c->stream));
       HIPCHK(c, hipMemcpyAsync(ks.modq[k].p, srcq[k], len[k], hipMemcpyDeviceToDevice, c->stream));
     }
-    std::vector<uint32_t> kg(n_keys, 0u);
-    if (key_group) for (uint32_t k = 0; k < n_keys; ++k) kg[k] = std::min(key_group[k], n_groups - 1u);
     if (ks.q_be.ensure_exact((size_t)n_groups * qbytes) != hipSuccess || ks.key_group.ensure_exact((size_t)n_keys * 4) != hipSuccess ||
         ks.tab.ensure_exact(ks.table_bytes()) != hipSuccess)
       return nomem();
     HIPCHK(c, hipMemcpyAsync(ks.q_be.p, q, (size_t)n_groups * qbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ks.key_group.p, kg.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, c->stream));
-    // the bases, g of every group and then y of every key, as one array of limbs (scratch of this call)
+    HIPCHK(c, hipMemcpyAsync(ks.key_group.p, hb.key_group.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, c->stream));
+    // the bases as one array of limbs (scratch of this call)
     const uint32_t n_bases = n_groups + n_keys;
-    std::vector<uint8_t> bases((size_t)n_bases * pbytes);
-    memcpy(bases.data(), g, (size_t)n_groups * pbytes);
-    memcpy(bases.data() + (size_t)n_groups * pbytes, keys_y, (size_t)n_keys * pbytes);
     uint32_t* d_bases;
-    if ((rc = to_dev_limbs(c, sb, bases.data(), n_bases, pbytes, &d_bases))) return rc;
-    const ModTab sp{ks.modp[0].as<uint32_t>(), ks.modp[1].as<uint32_t>(), ks.modp[2].as<uint32_t>(), nullptr};
+    if ((rc = to_dev_limbs(c, sb, hb.bases.data(), n_bases, pbytes, &d_bases))) return rc;
     const uint32_t parts = dsa_keyset_parts(ks.w);
     hipLaunchKernelGGL((k_dsav_comb_build<MONT_L, MONT_TPI>), quad_grid(n_bases * ks.windows * parts), dim3(RSA_BLOCK), 0, c->stream, n_groups, n_keys,
-                       (const uint32_t*)d_bases, ks.key_group.as<uint32_t>(), sp, ks.w, ks.windows, parts, ks.tab.as<uint32_t>());
+                       (const uint32_t*)d_bases, ks.key_group.as<uint32_t>(), ks.rows(ks.modp), ks.w, ks.windows, parts, ks.tab.as<uint32_t>());
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (the host vectors above die with this call)
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -137,11 +130,8 @@ int dsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const u
   ctx_lock lk(c->mu);
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if (n_ops) {                                 // fail closed: whatever refuses the call below leaves failures behind
-    if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
-    if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
-    else memset(valid_out, 0, n_ops);
-  }
+  VerdictOut vo{valid_out, status_out, n_ops, dev};
+  if ((rc = vo.fail_closed(c))) return rc;
   if (dlen == 0 || dlen > 64 || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
   KtRead kr(c);
   if (kr.rc) return kr.rc;
@@ -149,30 +139,12 @@ int dsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const u
   if (!ks) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
   if (n_ops == 0) return 0;
   ScratchBufs sb(c);
-  const ModTab mp{ks->modp[0].as<uint32_t>(), ks->modp[1].as<uint32_t>(), ks->modp[2].as<uint32_t>(), nullptr};
-  const ModTab mq{ks->modq[0].as<uint32_t>(), ks->modq[1].as<uint32_t>(), ks->modq[2].as<uint32_t>(), nullptr};
-  uint32_t* d_ki = nullptr;
-  uint8_t *d_dg, *d_sig;
-  void *d_e, *d_ok, *d_og, *d_flag, *d_valid, *d_st;
-  if (key_idx && (rc = to_dev(c, sb, key_idx, (size_t)n_ops, &d_ki, dev))) return rc;                  // clamped by k_dsav_prep
-  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
-  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * ks->qbytes, &d_sig, dev))) return rc;
-  if ((rc = dev_alloc(c, sb, (size_t)n_ops * DSAV_ROW * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * 4, &d_ok, false)) ||
-      (rc = dev_alloc(c, sb, (size_t)n_ops * 4, &d_og, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)))
-    return rc;
-  if (dev) { d_valid = valid_out; d_st = status_out; }
-  else if ((rc = dev_alloc(c, sb, n_ops, &d_valid, false)) || (rc = dev_alloc(c, sb, n_ops, &d_st, false))) return rc;
-  hipStream_t s = c->stream;
-  hipLaunchKernelGGL(k_dsav_prep, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint8_t*)d_dg, dlen, (const uint8_t*)d_sig, ks->qbytes,
-                     (const uint32_t*)d_ki, ks->n_keys, ks->key_group.as<uint32_t>(), ks->q_be.as<uint8_t>(), (uint32_t*)d_e, (uint32_t*)d_ok,
-                     (uint32_t*)d_og, (uint8_t*)d_flag, (uint8_t*)d_st);
-  hipLaunchKernelGGL((k_dsav_comb_exp<MONT_L, MONT_TPI>), quad_grid(n_ops), dim3(RSA_BLOCK), 0, s, n_ops, (const uint32_t*)d_e, (const uint32_t*)d_ok,
-                     (const uint32_t*)d_og, (const uint8_t*)d_flag, ks->n_groups, mp, mq, ks->tab.as<uint32_t>(), ks->w, ks->windows, (uint8_t*)d_valid);
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
-  }
-  return finish(c, dev);
+  DsavScratch w;
+  if ((rc = dsav_prep(c, sb, vo, digests, dlen, sigs, ks->qbytes, key_idx, ks->n_keys, ks->key_group.as<uint32_t>(), ks->q_be.as<uint8_t>(), &w))) return rc;
+  hipLaunchKernelGGL((k_dsav_comb_exp<MONT_L, MONT_TPI>), quad_grid(n_ops), dim3(RSA_BLOCK), 0, c->stream, n_ops, (const uint32_t*)w.e, (const uint32_t*)w.ok,
+                     (const uint32_t*)w.og, (const uint8_t*)w.flag, ks->n_groups, ks->rows(ks->modp), ks->rows(ks->modq), ks->tab.as<uint32_t>(), ks->w,
+                     ks->windows, (uint8_t*)vo.d_valid);
+  return vo.finish(c);
 }
 
 }  // namespace

@@ -70,6 +70,35 @@ int ec_status_failed(bftkv_gpu_ctx* c, uint8_t* status_out, uint32_t n_ops, bool
   return 0;
 }
 
+// The two result arrays of a verification call (verdict and status byte per signature), shared by the ECDSA and DSA impls.
+struct VerdictOut {
+  uint8_t *valid_out, *status_out;
+  uint32_t n_ops;
+  bool dev;
+  void *d_valid = nullptr, *d_st = nullptr;      // where the kernels write: the caller's device arrays, or scratch (device_arrays)
+  // fail closed: whatever refuses the call afterwards leaves failed statuses and zero verdicts behind
+  int fail_closed(bftkv_gpu_ctx* c) {
+    if (!n_ops) return 0;
+    if (int rc = ec_status_failed(c, status_out, n_ops, dev)) return rc;
+    if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
+    else memset(valid_out, 0, n_ops);
+    return 0;
+  }
+  int device_arrays(bftkv_gpu_ctx* c, ScratchBufs& sb) {
+    if (dev) { d_valid = valid_out; d_st = status_out; return 0; }
+    if (int rc = dev_alloc(c, sb, n_ops, &d_valid, false)) return rc;
+    return dev_alloc(c, sb, n_ops, &d_st, false);
+  }
+  // end of the call: a host caller's arrays are copied back and waited for
+  int finish(bftkv_gpu_ctx* c) {
+    if (!dev) {
+      HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, c->stream));
+    }
+    return ::finish(c, dev);
+  }
+};
+
 int ecdsa_calculate_r_impl(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
                            const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out, bool dev) {
   if (!c || !curve || bit_size == 0 || bit_size > 521 || k == 0 || k > 1024 || (uint64_t)n_ops * k > (1u << 24) ||
@@ -200,15 +229,14 @@ int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, 
   ctx_lock lk(c->mu);
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
-  if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
-  else memset(valid_out, 0, n_ops);
+  VerdictOut vo{valid_out, status_out, n_ops, dev};
+  if ((rc = vo.fail_closed(c))) return rc;
   ScratchBufs sb(c);
   { int grc = modtab_gc(c); if (grc) return grc; }
   ModTab mq;
   uint32_t *d_gi, *d_ki = nullptr;
   uint8_t *d_dg, *d_sig, *d_keys;
-  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2, *d_valid, *d_st;
+  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2;
   if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq))) return rc;                      // N, for k_modinv
   if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
   if (key_idx) {                                                                       // clamped on the device, for host callers too
@@ -221,8 +249,7 @@ int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, 
   if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
       (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
     return rc;
-  if (dev) { d_valid = valid_out; d_st = status_out; }
-  else if ((rc = dev_alloc(c, sb, n_ops, &d_valid, false)) || (rc = dev_alloc(c, sb, n_ops, &d_st, false))) return rc;
+  if ((rc = vo.device_arrays(c, sb))) return rc;
   hipStream_t s = c->stream;
   ec_dispatch(id, curve, [&](auto C) {
     constexpr int L = decltype(C)::kWords;
@@ -242,14 +269,10 @@ int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, 
     hipLaunchKernelGGL(k_ecv_base<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint32_t*)d_e, (const uint32_t*)d_w28,
                        (const uint8_t*)d_flag, C, tab, w, nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
     hipLaunchKernelGGL(k_ecv_key<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint8_t*)d_keys, (const uint32_t*)d_ki, n_keys,
-                       (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag, (const uint8_t*)d_ibad, C, (uint8_t*)d_valid, (uint8_t*)d_st);
+                       (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag, (const uint8_t*)d_ibad, C, (uint8_t*)vo.d_valid, (uint8_t*)vo.d_st);
   });
   if (rc) return rc;
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
-  }
-  return finish(c, dev);
+  return vo.finish(c);
 }
 
 // ---- resident key sets ----------------------------------------------------------------------------------------------------
@@ -387,11 +410,8 @@ int ecdsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const
   ctx_lock lk(c->mu);
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if (n_ops) {                                 // fail closed: whatever refuses the call below leaves failures behind
-    if ((rc = ec_status_failed(c, status_out, n_ops, dev))) return rc;
-    if (dev) HIPCHK(c, hipMemsetAsync(valid_out, 0, n_ops, c->stream));
-    else memset(valid_out, 0, n_ops);
-  }
+  VerdictOut vo{valid_out, status_out, n_ops, dev};
+  if ((rc = vo.fail_closed(c))) return rc;
   if (dlen == 0 || dlen > 66 || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
   KtRead kr(c);
   if (kr.rc) return kr.rc;
@@ -413,7 +433,7 @@ int ecdsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const
   mq.r2w_limbs = ks->mod[3].as<uint32_t>();
   uint32_t *d_gi, *d_ki = nullptr;
   uint8_t *d_dg, *d_sig;
-  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2, *d_valid, *d_st;
+  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2;
   if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
   if (key_idx) {                                                                       // clamped on the device, for host callers too
     uint32_t* raw;
@@ -424,8 +444,7 @@ int ecdsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const
   if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
       (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
     return rc;
-  if (dev) { d_valid = valid_out; d_st = status_out; }
-  else if ((rc = dev_alloc(c, sb, n_ops, &d_valid, false)) || (rc = dev_alloc(c, sb, n_ops, &d_st, false))) return rc;
+  if ((rc = vo.device_arrays(c, sb))) return rc;
   hipStream_t s = c->stream;
   ec_dispatch(id, ks->curve.data(), [&](auto C) {
     constexpr int L = decltype(C)::kWords;
@@ -442,14 +461,10 @@ int ecdsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const
                        (const uint8_t*)d_flag, C, gtab, ks->w, ks->nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
     hipLaunchKernelGGL(k_ecv_key_tab<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, ks->tab.as<uint32_t>(), ks->refused.as<uint8_t>(),
                        (const uint32_t*)d_ki, ks->n_keys, ks->w, ks->nwin, (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag,
-                       (const uint8_t*)d_ibad, C, (uint8_t*)d_valid, (uint8_t*)d_st);
+                       (const uint8_t*)d_ibad, C, (uint8_t*)vo.d_valid, (uint8_t*)vo.d_st);
   });
   if (rc) return rc;
-  if (!dev) {
-    HIPCHK(c, hipMemcpyAsync(valid_out, d_valid, n_ops, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(status_out, d_st, n_ops, hipMemcpyDeviceToHost, s));
-  }
-  return finish(c, dev);
+  return vo.finish(c);
 }
 
 }  // namespace

@@ -54,6 +54,8 @@ EXPORTS = [
     "bftkv_gpu_ecdsa_verify_keyset_dev", "bftkv_gpu_batcher_ecdsa_verify_keyset", "bftkv_gpu_selftest_ecdsa_keyset_table",
     "bftkv_gpu_dsa_keyset_create", "bftkv_gpu_dsa_keyset_destroy", "bftkv_gpu_dsa_keyset_info", "bftkv_gpu_dsa_verify_keyset",
     "bftkv_gpu_dsa_verify_keyset_dev", "bftkv_gpu_batcher_dsa_verify_keyset", "bftkv_gpu_selftest_dsa_keyset_table",
+    "bftkv_gpu_rsa_verify", "bftkv_gpu_rsa_verify_dev", "bftkv_gpu_rsa_keyset_create", "bftkv_gpu_rsa_keyset_destroy", "bftkv_gpu_rsa_keyset_info",
+    "bftkv_gpu_rsa_verify_keyset", "bftkv_gpu_rsa_verify_keyset_dev", "bftkv_gpu_batcher_rsa_verify", "bftkv_gpu_batcher_rsa_verify_keyset",
 ]
 
 _lib = None
@@ -164,6 +166,15 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_dsa_verify_keyset_dev.argtypes = lib.bftkv_gpu_dsa_verify_keyset.argtypes
     lib.bftkv_gpu_batcher_dsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, u8p, u8p]
     lib.bftkv_gpu_selftest_dsa_keyset_table.argtypes = [vp, C.c_int, u32, vp, C.c_uint64]
+    lib.bftkv_gpu_rsa_verify.argtypes = [vp, u32, u8p, u32, u32, u8p, u32, vp, u32, u8p, vp, u8p, u8p]
+    lib.bftkv_gpu_rsa_verify_dev.argtypes = lib.bftkv_gpu_rsa_verify.argtypes
+    lib.bftkv_gpu_rsa_keyset_create.argtypes = [vp, u32, u8p, vp, u32, C.POINTER(C.c_int)]
+    lib.bftkv_gpu_rsa_keyset_destroy.argtypes = [vp, C.c_int]
+    lib.bftkv_gpu_rsa_keyset_info.argtypes = [vp, C.c_int] + [C.POINTER(u32)] * 3
+    lib.bftkv_gpu_rsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u32, u8p, vp, u8p, u8p]
+    lib.bftkv_gpu_rsa_verify_keyset_dev.argtypes = lib.bftkv_gpu_rsa_verify_keyset.argtypes
+    lib.bftkv_gpu_batcher_rsa_verify.argtypes = [vp, u8p, u32, u32, u8p, u32, u8p, u32, u8p, u8p]
+    lib.bftkv_gpu_batcher_rsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u32, u8p, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -751,6 +762,60 @@ class Context:
         self._check(self.lib.bftkv_gpu_selftest_dsa_keyset_table(self.h, keyset, base, words.ctypes.data, len(words)), "selftest_dsa_keyset_table")
         return words.reshape(info["windows"], nent, 76)
 
+    def rsa_verify(self, digests, sigs, keys, hash_id: int, key_idx=None, nbytes=None):
+        """rsa.VerifyPKCS1v15 on raw signatures: digests [n_ops] bytes of ONE length (the size of hash_id's hash; 1..64 for hash_id
+        0, no prefix), sigs [n_ops] bytes of nbytes each, keys [(n, e)] ints, key_idx [n_ops] or None (key 0) -> (valid, status),
+        uint8 each.  nbytes defaults to the length of a signature, or to the widest modulus."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        if nbytes is None:
+            nbytes = len(sigs[0]) if n else max(1, max((int(k[0]).bit_length() + 7) // 8 for k in keys))
+        if any(len(d) != dlen for d in digests) or any(len(s) != nbytes for s in sigs) or len(sigs) != n:
+            raise ValueError("rsa_verify: digests of one length, sigs of nbytes")
+        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
+        kn = _ints_to_be([k[0] for k in keys], nbytes)
+        ke = np.ascontiguousarray([k[1] for k in keys], dtype=np.uint32)
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_rsa_verify(self.h, n, _ptr(dg), hash_id, dlen, _ptr(sg), nbytes, None if ki is None else _ptr(ki), len(keys),
+                                                  _ptr(kn), _ptr(ke), _ptr(valid), _ptr(st)), "rsa_verify")
+        return valid[:n], st[:n]
+
+    def rsa_keyset_create(self, keys, nbytes=None) -> int:
+        """Register keys [(n, e)] ints once: their Montgomery rows stay on the device.  An even modulus does not refuse the set
+        (rsa_keyset_info counts it; its signatures are fenced, or refused by the length rule).  nbytes defaults to the widest modulus."""
+        if nbytes is None:
+            nbytes = max(1, max((int(k[0]).bit_length() + 7) // 8 for k in keys))
+        kn = _ints_to_be([k[0] for k in keys], nbytes)
+        ke = np.ascontiguousarray([k[1] for k in keys], dtype=np.uint32)
+        h = C.c_int(-1)
+        self._check(self.lib.bftkv_gpu_rsa_keyset_create(self.h, len(keys), _ptr(kn), _ptr(ke), nbytes, C.byref(h)), "rsa_keyset_create")
+        return h.value
+
+    def rsa_keyset_destroy(self, keyset: int):
+        self._check(self.lib.bftkv_gpu_rsa_keyset_destroy(self.h, keyset), "rsa_keyset_destroy")
+
+    def rsa_keyset_info(self, keyset: int):
+        """-> {n_keys, n_refused, nbytes}"""
+        v = [C.c_uint32() for _ in range(3)]
+        self._check(self.lib.bftkv_gpu_rsa_keyset_info(self.h, keyset, *[C.byref(x) for x in v]), "rsa_keyset_info")
+        return dict(zip(("n_keys", "n_refused", "nbytes"), (x.value for x in v)))
+
+    def rsa_verify_keyset(self, keyset: int, digests, sigs, hash_id: int, key_idx=None):
+        """rsa_verify under the keys of a set: digests [n_ops] bytes of ONE length, sigs [n_ops] bytes of the set's nbytes, key_idx
+        [n_ops] into the set or None (key 0) -> (valid, status), uint8 each."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        slen = self.rsa_keyset_info(keyset)["nbytes"]
+        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or len(sigs) != n:
+            raise ValueError("rsa_verify_keyset: digests of one length, sigs of the set's nbytes")
+        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_rsa_verify_keyset(self.h, keyset, n, _ptr(dg), hash_id, dlen, _ptr(sg), None if ki is None else _ptr(ki),
+                                                         _ptr(valid), _ptr(st)), "rsa_verify_keyset")
+        return valid[:n], st[:n]
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -908,6 +973,24 @@ class Batcher:
         dg, sg = _u8(digest), _u8(sig)
         valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
         rc = self.lib.bftkv_gpu_batcher_dsa_verify_keyset(self.h, keyset, key, _ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
+
+    def rsa_verify(self, digest: bytes, sig: bytes, n: int, e: int, hash_id: int):
+        """rsa.VerifyPKCS1v15 for one raw signature (nbytes = len(sig)) under (n, e) -> (rc, status, valid)."""
+        if not digest or not sig:
+            raise ValueError("rsa_verify: a non-empty digest and signature")
+        dg, sg, nn = _u8(digest), _u8(sig), _ints_to_be([n], len(sig))
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_rsa_verify(self.h, _ptr(dg), hash_id, len(digest), _ptr(sg), len(sig), _ptr(nn), e, _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
+
+    def rsa_verify_keyset(self, keyset: int, key: int, digest: bytes, sig: bytes, hash_id: int):
+        """rsa.VerifyPKCS1v15 for one raw signature under key `key` of a resident RSA key set -> (rc, status, valid)."""
+        if not digest or len(sig) != self.ctx.rsa_keyset_info(keyset)["nbytes"]:
+            raise ValueError("rsa_verify_keyset: sig of the set's nbytes, a non-empty digest")
+        dg, sg = _u8(digest), _u8(sig)
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_rsa_verify_keyset(self.h, keyset, key, _ptr(dg), hash_id, len(digest), _ptr(sg), _ptr(valid), _ptr(st))
         return rc, int(st[0]), int(valid[0])
 
     def modexp(self, base: int, exp: int, mod: int, nbytes: int = 256, exp_len: int = 32):

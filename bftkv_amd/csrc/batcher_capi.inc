@@ -278,7 +278,7 @@ struct bftkv_gpu_batcher {
   enum class Kind {
     Collective, Signature, Message, Cert,                      // CollectiveSignature.Verify, Signature.Verify, a transport message, Issuer + VerifyWithCertificate
     ModmulProduct, LagrangeCombine, DsaCalculateR, Modexp,     // ONE share-combine operation: prod psig mod N, sum l_j y_j mod m, CalculateR, b^x mod n
-    EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset
+    EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset, RsaVerify, RsaVerifyKeyset
   };
   static bool hashed_by_caller(Kind k) { return k == Kind::Collective || k == Kind::Signature; }      // a SHA-256 midstate of tbs goes to the device, not tbs
   static bool threshold_style(Kind k) { return k >= Kind::ModmulProduct; }      // th_* fields in, a BFTKV_TH_* status byte and th_out out
@@ -298,6 +298,8 @@ struct bftkv_gpu_batcher {
   //   EcdsaVerifyKeyset         set     dlen  -          -          -      digest          r|s (2 f)   -       -              -           key     verdict
   //   DsaVerify                 -       dlen  pb         qb         -      digest          r|s (2 qb)  p       q              g, y (pb)   -       verdict
   //   DsaVerifyKeyset           set     dlen  -          -          -      digest          r|s (2 qb)  -       -              -           key     verdict
+  //   RsaVerify                 -       dlen  nbytes     hash id    -      digest          s (nbytes)  n       -              -           e       verdict
+  //   RsaVerifyKeyset           set     dlen  -          hash id    -      digest          s (nbytes)  -       -              -           key     verdict
   // An EcdsaCalculateR or EcdsaVerify group shares one recognised curve, which the device call takes by value: its bit size is part of
   // the shape.  A key-set group shares the set: the lane is a fork and passes the handle through.
   struct Req {
@@ -332,7 +334,7 @@ struct bftkv_gpu_batcher {
     const int32_t* th_xs = nullptr;
     const uint8_t *th_a = nullptr, *th_b = nullptr, *th_mod = nullptr, *th_mod2 = nullptr;
     uint8_t* th_out = nullptr;
-    uint32_t ks_key = 0;       // the key's index within the set
+    uint32_t ks_key = 0;       // the key's index within the set (RsaVerify: the public exponent)
     const uint8_t *th_g = nullptr, *th_y = nullptr;
   };
   struct Batch {
@@ -571,6 +573,28 @@ struct bftkv_gpu_batcher {
     publish_verdicts(g, rc, st.data(), valid.data());
   }
 
+  // RsaVerify: a group's callers share (nbytes, hash id, dlen), whatever their keys.  The distinct (n, e) of the group make the call's
+  // key table in first-seen order; a recurring modulus finds its rows in the context's cache by value.
+  void run_rsa_verify(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k, nb = r0.th_nbytes, hash_id = r0.th_qbytes;
+    std::map<std::string, uint32_t> slot;
+    const std::vector<uint8_t> dg = gather(g, &Req::th_a, dlen), sg = gather(g, &Req::th_b, nb);
+    std::vector<uint8_t> keys_n, valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
+    std::vector<uint32_t> idx(n), keys_e;
+    for (uint32_t i = 0; i < n; ++i) {
+      std::string kk((const char*)g[i]->th_mod, nb);
+      kk.append((const char*)&g[i]->ks_key, 4);
+      auto ins = slot.emplace(std::move(kk), (uint32_t)slot.size());
+      if (ins.second) { keys_n.insert(keys_n.end(), g[i]->th_mod, g[i]->th_mod + nb); keys_e.push_back(g[i]->ks_key); }
+      idx[i] = ins.first->second;
+    }
+    const int rc = rsa_verify_impl(lane.ctx, n, dg.data(), hash_id, dlen, sg.data(), nb, idx.data(), (uint32_t)slot.size(), keys_n.data(), keys_e.data(),
+                                   valid.data(), st.data(), false);
+    ++device_calls;
+    publish_verdicts(g, rc, st.data(), valid.data());
+  }
+
   // DsaVerify: a group's callers share the widths and the digest length, whatever their groups and keys.  The distinct (p, q, g) of
   // the batch make the call's group table in BYTE ORDER (the same groups find their Montgomery rows in the context's cache call after
   // call), the distinct (group, y) its key table in first-seen order.
@@ -693,6 +717,16 @@ struct bftkv_gpu_batcher {
             return ks ? 2 * (size_t)ks->qbytes : 0;
           }, dsa_verify_keyset_impl);
           break;
+        case Kind::RsaVerify: run_rsa_verify(lane, g, calls); break;
+        case Kind::RsaVerifyKeyset: {
+          const uint32_t hash_id = g[0]->th_qbytes;
+          run_verify_keyset(lane, g, calls, [](const bftkv_gpu_ctx* c, int set) {
+            const RsaKeySet* ks = rsa_keyset_find(c, set);
+            return ks ? (size_t)ks->nbytes : 0;
+          }, [hash_id](bftkv_gpu_ctx* c, int set, uint32_t n, const uint8_t* dg, uint32_t dlen, const uint8_t* sg, const uint32_t* idx, uint8_t* valid,
+                       uint8_t* st, bool dev) { return rsa_verify_keyset_impl(c, set, n, dg, hash_id, dlen, sg, idx, valid, st, dev); });
+          break;
+        }
       }
     }
     return calls;
@@ -1035,6 +1069,26 @@ int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, ui
   bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::DsaVerify, bftkv_gpu_batcher::NO_QUORUM, dlen, pbytes, qbytes);
   r.th_k = dlen; r.th_nbytes = pbytes; r.th_qbytes = qbytes; r.th_a = digest; r.th_b = sig; r.th_mod = p; r.th_mod2 = q; r.th_g = g; r.th_y = y;
   r.th_out = valid_out;
+  return verdict_submit(b, r, status_out);
+}
+
+// A caller whose (hash id, dlen, nbytes) the batched entry would refuse for the WHOLE call is refused here alone, before it joins a batch.
+int bftkv_gpu_batcher_rsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t hash_id, uint32_t dlen, const uint8_t* sig, uint32_t nbytes,
+                                 const uint8_t* n, uint32_t e, uint8_t* valid_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (valid_out) *valid_out = 0;
+  if (!b || !status_out || !valid_out || !digest || !sig || !n || !rsav_shape_ok(hash_id, dlen, nbytes)) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::RsaVerify, bftkv_gpu_batcher::NO_QUORUM, dlen, nbytes, hash_id);
+  r.th_k = dlen; r.th_nbytes = nbytes; r.th_qbytes = hash_id; r.th_a = digest; r.th_b = sig; r.th_mod = n; r.ks_key = e; r.th_out = valid_out;
+  return verdict_submit(b, r, status_out);
+}
+int bftkv_gpu_batcher_rsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t hash_id, uint32_t dlen,
+                                        const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (valid_out) *valid_out = 0;
+  if (!b || !status_out || !valid_out || !digest || !sig || !rsav_shape_ok(hash_id, dlen, 1)) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::RsaVerifyKeyset, keyset, dlen, hash_id);
+  r.th_k = dlen; r.th_qbytes = hash_id; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
   return verdict_submit(b, r, status_out);
 }
 

@@ -36,6 +36,7 @@
 #include "threshold_kernels.hip"
 #include "ec_kernels.hip"
 #include "dsa_verify_kernels.hip"
+#include "rsa_verify_kernels.hip"
 
 using namespace bftkv;
 
@@ -120,6 +121,16 @@ struct DsaKeySet {
   void release() { tab.release(); q_be.release(); key_group.release(); for (DevBuf& b : modp) b.release(); for (DevBuf& b : modq) b.release(); }
 };
 
+// A resident RSA key set (rsa_verify_capi.inc): the keys' Montgomery rows in both forms of k_rsav_verify.  An even modulus has
+// zero rows and is counted in n_refused.
+struct RsaKeySet {
+  bool live = false;
+  uint32_t n_keys = 0, n_refused = 0, nbytes = 0;
+  DevBuf n29, r2_29, n80, r2_80;           // [n_keys][72] limbs of 29 bits (R = 2^2088); [n_keys][80] limbs of 28 bits (R = 2^2240)
+  DevBuf meta;                             // [n_keys] uint4: -n^-1 mod 2^29, k = ceil(bits(n) / 8), e, 1 for an even n
+  void release() { n29.release(); r2_29.release(); n80.release(); r2_80.release(); meta.release(); }
+};
+
 }  // namespace
 
 using ctx_lock = std::lock_guard<std::recursive_mutex>;
@@ -177,6 +188,7 @@ struct bftkv_gpu_ctx {
   std::vector<QuorumHost> quorums;
   std::vector<EcKeySet> ec_keysets;    // root: the handles of bftkv_gpu_ecdsa_keyset_create; forks read them under KtRead, without a copy
   std::vector<DsaKeySet> dsa_keysets;  // root: the handles of bftkv_gpu_dsa_keyset_create (a space of their own), read the same way
+  std::vector<RsaKeySet> rsa_keysets;  // root: the handles of bftkv_gpu_rsa_keyset_create (a space of their own), read the same way
 
   // per-call arena
   DevBuf txt_mid32, txt_mid64, txt_tail, txt_len;     // text-mode hashing state (TextDev)
@@ -195,12 +207,14 @@ struct bftkv_gpu_ctx {
   uint32_t ec_fb_w[4] = {};           // ... and its window width (0: not built)
   uint32_t multiexp_block = 0;        // experiment knob (BFTKV_MULTIEXP_BLOCK = 64): one-wave blocks for the 4-lane k_multiexp
   uint32_t multiexp_lanes = 0;        // experiment knob (BFTKV_MULTIEXP_LANES = 4 | 8): lanes per number in k_multiexp, 0 = by call size
+  uint32_t rsav_lanes = 0;            // experiment knob (BFTKV_RSAV_LANES = 4 | 8): lanes per signature in k_rsav_verify, 0 = by call size
   uint32_t dsa_inv_mode = 0;          // experiment knob (BFTKV_DSA_INV = single | batched): 1 / 2, 0 = by batch shape
   uint32_t n_cus = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   uint32_t lagrange_x_bound = 0;      // bftkv_gpu_set_lagrange_x_bound: device-resident callers promise 0 <= x <= bound (0: no promise)
   bool early_exit = true;              // CollectiveSignature.Verify stops verifying where the reference stops reading (bftkv_gpu_set_early_exit)
   std::vector<DevBuf*> scratch_pool;   // threshold entry points' temporaries (threshold_capi.inc)
   std::unordered_map<std::string, std::vector<uint32_t>> modrow_cache;   // ... and the host-computed rows of ONE modulus (n, R^2, -n^-1, R_wide^2), by its bytes
+  std::unordered_map<std::string, std::vector<uint32_t>> rsav_row_cache[2];   // RSA verification: n and R^2 mod n of ONE modulus by its bytes, [0] 72 limbs of 29 bits, [1] 80 of 28
   std::map<std::string, std::array<DevBuf, 4>> modtab_cache;   // Montgomery tables of the threshold entry points, by modulus bytes
   uint32_t* h_mail = nullptr;          // pinned + mapped: [0] packet count of the call in flight (k_scan_counts)
   uint32_t* d_mail = nullptr;
@@ -1246,6 +1260,7 @@ int bftkv_gpu_init(int device_ordinal, bftkv_gpu_ctx** out) {
   if (const char* e = getenv("BFTKV_EC_SPLIT")) c->ec_split = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_EC_WINDOW")) c->ec_window = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_LANES")) c->multiexp_lanes = (uint32_t)atoi(e);
+  if (const char* e = getenv("BFTKV_RSAV_LANES")) c->rsav_lanes = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_BLOCK")) c->multiexp_block = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_DSA_INV")) c->dsa_inv_mode = !strcmp(e, "batched") ? 2u : !strcmp(e, "single") ? 1u : 0u;
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0) c->n_cus = (uint32_t)cus; }
@@ -1291,6 +1306,7 @@ void bftkv_gpu_destroy(bftkv_gpu_ctx* c) {
   for (auto& q : c->quorums) { q.member.release(); q.ids.release(); }
   for (EcKeySet& ks : c->ec_keysets) ks.release();
   for (DsaKeySet& ks : c->dsa_keysets) ks.release();
+  for (RsaKeySet& ks : c->rsa_keysets) ks.release();
   c->in_pack.release();
   c->forced_iss.release();
   release_small_pin(c);
@@ -2347,6 +2363,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "ec_capi.inc"
 #include "dsa_verify_capi.inc"
 #include "dsa_keyset_capi.inc"
+#include "rsa_verify_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

@@ -415,6 +415,19 @@ int bftkv_gpu_batcher_dsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, ui
  * handle names when the request RUNS: the caller must not destroy a set while calls that name it are in flight. */
 int bftkv_gpu_batcher_dsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t dlen,
                                         const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
+/* rsa.VerifyPKCS1v15 for ONE raw signature (bftkv_gpu_rsa_verify): digest [dlen], sig and n [nbytes] big-endian, e the public
+ * exponent.  Callers are grouped by (nbytes, hash_id, dlen), whatever their keys.  What bftkv_gpu_rsa_verify refuses for the whole
+ * call (an unknown hash_id, a dlen that is not the hash's, nbytes 0 or > 256, a NULL array) returns BFTKV_E_INVALID for that caller
+ * alone, before it joins a batch; an even modulus is no refusal (status BFTKV_TH_FENCED, or BFTKV_TH_OK by the length rule).
+ * Whenever the return code is not 0, *status_out is BFTKV_TH_FAILED and *valid_out 0. */
+int bftkv_gpu_batcher_rsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, uint32_t hash_id, uint32_t dlen, const uint8_t* sig,
+                                 uint32_t nbytes, const uint8_t* n, uint32_t e, uint8_t* valid_out, uint8_t* status_out);
+/* The same under key `key` of a resident RSA key set (bftkv_gpu_rsa_keyset_create on the batcher's context): sig [nbytes of the set];
+ * an index past the set is clamped to its last key.  Callers are grouped by (key set, hash_id, dlen).  An unknown or destroyed handle
+ * returns BFTKV_E_INVALID for its own group alone.  The lane reads nbytes of `sig` for the set the handle names when the request
+ * RUNS: the caller must not destroy a set while calls that name it are in flight. */
+int bftkv_gpu_batcher_rsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t hash_id, uint32_t dlen,
+                                        const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -694,6 +707,51 @@ int bftkv_gpu_dsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_o
  * x 76 32-bit words.  BFTKV_E_NOMEM when cap_words is less than that, BFTKV_E_INVALID for a base past the set.  The tests compare
  * it with a table built by pow(). */
 int bftkv_gpu_selftest_dsa_keyset_table(bftkv_gpu_ctx* ctx, int keyset, uint32_t base, uint32_t* words_out, uint64_t cap_words);
+
+/* ---- raw RSA PKCS#1 v1.5 verification (docs/parity.md "RSA verification") ------------------------
+ * Go 1.13's rsa.VerifyPKCS1v15(pub, hash, hashed, sig) on raw inputs, for moduli of at most 2048 bits: "is the combined threshold
+ * signature good under the CA's (N, e)?" (rsaProc.ProcessResponse, crypto/threshold/rsa/rsa.go:235-253).
+ *   digests [n_ops][dlen]; hash_id: an OpenPGP hash id (1 MD5, 2 SHA-1, 3 RIPEMD-160 with Go's identifier, 8 SHA-256, 9 SHA-384,
+ *   10 SHA-512, 11 SHA-224) whose DigestInfo prefix goes in front of the digest, dlen the hash's size; or 0 for no prefix (Go's
+ *   crypto.Hash(0)), the digest taken as it stands with 1 <= dlen <= 64.  No availability policy applies: nothing is hashed.
+ *   sigs [n_ops][nbytes] big-endian, ANY value: s >= n is reduced as math/big reduces it (Go <= 1.13 checks neither s < n nor the
+ *   signature's length).  key_idx [n_ops] (NULL: key 0; an index past the table is clamped to the last key).
+ *   keys_n [n_keys][nbytes] big-endian moduli, keys_e [n_keys] public exponents, any 32-bit value (e = 0 gives 1, hence verdict 0).
+ * Per signature, with k = ceil(bits(n) / 8) and tLen = prefix length + dlen, in this order:
+ *   k < tLen + 11 (n = 0 and n = 1 included)      valid 0, BFTKV_TH_OK      (Go refuses before any arithmetic, whatever n's parity)
+ *   n even                                        valid 0, BFTKV_TH_FENCED  (no statement about the reference)
+ *   otherwise                                     valid = (s^e mod n, left-padded to k bytes, == 00 01 FF .. FF 00 | prefix | digest), BFTKV_TH_OK
+ * One call has one (hash_id, dlen, nbytes).  BFTKV_E_INVALID for the call -- every verdict 0, every status BFTKV_TH_FAILED -- on an
+ * unknown hash_id, a dlen that is not the hash's size, nbytes 0 or > 256, n_keys 0 or a NULL array.  Outputs, fail-closed behaviour,
+ * the _dev form and return codes are those of bftkv_gpu_dsa_verify: nothing past n_ops is written; n_ops = 0 returns 0. */
+int bftkv_gpu_rsa_verify(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen, const uint8_t* sigs,
+                         uint32_t nbytes, const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys_n, const uint32_t* keys_e,
+                         uint8_t* valid_out, uint8_t* status_out);
+/* same with digests / sigs / key_idx / valid_out / status_out resident in HBM (keys_n and keys_e stay host pointers); asynchronous
+ * on the context's stream */
+int bftkv_gpu_rsa_verify_dev(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen, const uint8_t* sigs,
+                             uint32_t nbytes, const uint32_t* key_idx, uint32_t n_keys, const uint8_t* keys_n, const uint32_t* keys_e,
+                             uint8_t* valid_out, uint8_t* status_out);
+/* Resident RSA key sets: the keys of bftkv_gpu_rsa_verify registered once (the CA key of a threshold RSA signature).  The set keeps
+ * the keys' Montgomery rows on the device in both forms of the kernel, so a verification uploads only digests, signatures and
+ * indices.  1 <= n_keys <= 2^20, 1 <= nbytes <= 256 (fixed for the set's life: signatures are [n_ops][nbytes]).  An even modulus
+ * does not refuse registration: it gets no rows, bftkv_gpu_rsa_keyset_info counts it in n_refused_out, and signatures that name it
+ * are answered by the rules above (BFTKV_TH_FENCED, or BFTKV_TH_OK by the length rule).  Ownership, locking, handle space and error
+ * codes are those of the DSA key sets: created and destroyed on the root context (a fork: BFTKV_E_STATE), read by its forks and
+ * batcher lanes, handles a space of their own, a destroyed handle BFTKV_E_INVALID and handed out again by a later create. */
+int bftkv_gpu_rsa_keyset_create(bftkv_gpu_ctx* ctx, uint32_t n_keys, const uint8_t* keys_n, const uint32_t* keys_e, uint32_t nbytes,
+                                int* keyset_out);
+int bftkv_gpu_rsa_keyset_destroy(bftkv_gpu_ctx* ctx, int keyset);
+/* any of the outputs may be NULL */
+int bftkv_gpu_rsa_keyset_info(bftkv_gpu_ctx* ctx, int keyset, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* nbytes_out);
+/* bftkv_gpu_rsa_verify under the keys of a set: identical answers for identical bytes.  key_idx [n_ops] indexes the set (NULL: key
+ * 0, clamped); sigs are [n_ops][nbytes of the set].  Whenever the return code is not 0 (a bad handle included) every status is
+ * BFTKV_TH_FAILED and every verdict 0. */
+int bftkv_gpu_rsa_verify_keyset(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen,
+                                const uint8_t* sigs, const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+/* same with the per-signature arrays resident in HBM: nothing is read from host memory, the call never waits */
+int bftkv_gpu_rsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen,
+                                    const uint8_t* sigs, const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

@@ -2,7 +2,7 @@
 
     corpus(name) -> [Case]      Case = (label, group, key, digest, sig, expect)
 
-group is one of "honest", "mutation", "keyflip", "boundary", "constructed"; expect is "valid", "invalid", "fenced" where the
+group is one of "honest", "mutation", "keyflip", "boundary", "constructed", "special_x"; expect is "valid", "invalid", "fenced" where the
 construction fixes the answer, else None (the restatement decides).  Every digest length of the corpus is one of DLENS, so a
 test can hand the cases of one length to one device call."""
 import functools
@@ -155,6 +155,29 @@ def corpus(name: str):
         r, s = sign(c, d1, dg, rnd(rng, c))
         cases.append(Case(f"e = 0 dlen={dlen}", "constructed", k1, dg, sig_bytes(c, r, s), "fenced"))
     cases.append(Case("e = N", "constructed", k1, digest_for(c, n), sig_bytes(c, *E.ecdsa_sign_hash_int(c, d1, 0, rnd(rng, c))), "fenced"))
+    return tuple(cases) + special_x(name)
+
+
+def special_x(name: str):
+    """The group "special_x", behind everything else and from a generator of its own: valid signatures whose R = u1 G + u2 Q is each
+    special-x point of tests/ec_form_cases.py (smallest and largest x, Montgomery-form x next to p - 1 and to 2^(32 L - 1)), built as
+    the constructed cases above (Q = b^-1 (R - a G), r = x mod N, s = r / b, e = a s), and the same signatures with r + 1.  Where the
+    smallest x is 0 (P-256, P-384, P-521) r = 0 and no valid signature exists: the case stands as INVALID, and its r + 1 twin
+    (s = 1 / b) is the one that takes x(R) = 0 through the comparison."""
+    import ec_form_cases as F           # (it imports this module for sqrt_mod)
+    c = E.CURVES[name]
+    n = c["n"]
+    rng = np.random.default_rng(30260 + c["bit_size"])
+    cases = []
+    for label, (x, y) in F.special_x_points(name):
+        a, b = rnd(rng, c) or 1, rnd(rng, c) or 1
+        rpt = point_sub(c, (x, y), E.scalar_base_mult(c, a))
+        q = E.scalar_mult(c, rpt[0], rpt[1], E.int_bytes(pow(b, -1, n)))
+        r = x % n
+        s = (r or 1) * pow(b, -1, n) % n            # (r = 0: with r + 1 = 1 the device still computes that R, and x(R) = 0 is not 1)
+        dg = digest_for(c, a * s % n)
+        cases.append(Case(f"R of {label}", "special_x", E.marshal(c, *q), dg, sig_bytes(c, r, s), "valid" if r else "invalid"))
+        cases.append(Case(f"R of {label}, r + 1", "special_x", E.marshal(c, *q), dg, sig_bytes(c, r + 1, s), "invalid"))
     return tuple(cases)
 
 

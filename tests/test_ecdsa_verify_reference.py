@@ -54,6 +54,11 @@ def openssl_verify(lib, name, key: bytes, digest: bytes, sig: bytes):
         lib.ERR_clear_error()
 
 
+def _special_points(name):
+    import ec_form_cases as F
+    return F.special_x_points(name)
+
+
 @pytest.mark.parametrize("name", E.NAMES)
 def test_restatement_against_openssl_over_the_corpus(ossl, name):
     c = E.CURVES[name]
@@ -76,6 +81,19 @@ def test_restatement_against_openssl_over_the_corpus(ossl, name):
     labels = {cs.label for cs in cases}
     assert {"x(R) >= N #0", "u1 G = u2 Q", "u1 G = -u2 Q", "e = 0 dlen=32", "r = N", "s = 0xFF.."} <= labels
     assert dict(recorded)["u1 G = u2 Q"] is True          # the doubling case is a valid signature mathematically
+    # the group "special_x": R at the smallest and largest x and at the Montgomery-form x next to p - 1 and 2^(32 L - 1), each with r + 1
+    special = [cs for cs in cases if cs.group == "special_x"]
+    assert special == list(cases[-len(special):]) and len(special) == (6 if name == "P-521" else 8)
+    assert [cs.expect for cs in special[1::2]] == ["invalid"] * (len(special) // 2)
+    assert [cs.expect for cs in special[0::2]] == (["valid"] if name == "P-224" else ["invalid"]) + ["valid"] * (len(special) // 2 - 1)
+    for cs in special:
+        u1, u2 = V.hash_to_int(c, cs.digest), V.split_sig(c, cs.sig)[0]
+        w = pow(V.split_sig(c, cs.sig)[1], -1, c["n"])
+        q = E.unmarshal(c, cs.key)
+        rpt = E.add(c, *E.scalar_base_mult(c, u1 * w % c["n"]), *E.scalar_mult(c, q[0], q[1], E.int_bytes(u2 * w % c["n"])))
+        # R = u1 G + u2 Q is the special point; with r + 1 it is another, but for x = 0 (r = 0 is refused, s = 1 / b, so r + 1 = 1 gives that R)
+        if u2 and ("r + 1" not in cs.label or cs.label.startswith("R of smallest x = 0")):
+            assert rpt in [pt for _, pt in _special_points(name)], (name, cs.label)
 
 
 @pytest.mark.parametrize("name", E.NAMES)

@@ -59,6 +59,8 @@ def test_corpus(gpu_ctx, name):
         bad = [(cs.label, wt, g, r) for cs, wt, g, r in zip(cases, want, got, raw) if not wt == g == r]
         assert not bad, (name, bad)
         assert sum(wt == (1, V.OK) for wt in want) >= 14 and sum(wt[1] == V.FENCED for wt in want) >= 8
+        assert sum(cs.group == "special_x" and wt == (1, V.OK) for cs, wt in zip(cases, want)) >= 2     # R at the special x
+        assert sum(cs.group == "special_x" and wt == (0, V.OK) for cs, wt in zip(cases, want)) >= 3     # ... and with r + 1
     finally:
         gpu_ctx.ecdsa_keyset_destroy(ks)
 

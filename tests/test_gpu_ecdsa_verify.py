@@ -42,6 +42,8 @@ def test_corpus(gpu_ctx, name):
     bad = [(cs.label, w, g) for cs, w, g in zip(cases, want, got) if w != g]
     assert not bad, (name, bad)
     assert sum(w == (1, V.OK) for w in want) >= 14 and sum(w[1] == V.FENCED for w in want) >= 8
+    assert sum(cs.group == "special_x" and w == (1, V.OK) for cs, w in zip(cases, want)) >= 2           # R at the special x
+    assert sum(cs.group == "special_x" and w == (0, V.OK) for cs, w in zip(cases, want)) >= 3           # ... and with r + 1
     # a lone call, and NULL key_idx meaning key 0
     for i in (0, len(cases) - 1):
         cs = cases[i]

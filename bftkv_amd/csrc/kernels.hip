@@ -25,6 +25,7 @@
 
 #include "device_types.h"
 #include "mont28.h"
+#include "value_load.h"
 #include "u256.h"
 #include "hashes.h"
 
@@ -1436,9 +1437,19 @@ __global__ void __launch_bounds__(MODEXP_BLOCK, 3) k_rsa_modexp(const uint8_t* _
   {
     const uint32_t nb = (rec.mpi_bits[0] + 7u) >> 3;
     const uint8_t* mp = sig_blob + rec.body_off + rec.mpi_off[0];
-    auto sig_b = [&](uint32_t i) -> uint32_t { return i < nb ? mp[nb - 1 - i] : 0u; };
+    if constexpr (VALUE_LOAD_DWORDS) {
+      // unaligned dwords, all in flight before the first is used (value_load.h); nothing outside [mp, mp + nb) is read
+      uint32_t x[L];
+      value_limbs<W, L, TPI>(x, nb, qlane,
+                             [&](uint32_t o) -> uint32_t { uint32_t v; __builtin_memcpy(&v, mp + o, 4); return v; },
+                             [&](uint32_t o) -> uint32_t { return mp[o]; });
 #pragma unroll
-    for (int k = 0; k < L; ++k) x_lds[k] = limb_of<W>(sig_b, qlane * L + k);
+      for (int k = 0; k < L; ++k) x_lds[k] = x[k];
+    } else {
+      auto sig_b = [&](uint32_t i) -> uint32_t { return i < nb ? mp[nb - 1 - i] : 0u; };
+#pragma unroll
+      for (int k = 0; k < L; ++k) x_lds[k] = limb_of<W>(sig_b, qlane * L + k);
+    }
   }
   const uint32_t n0inv = W == 29 ? kt.n0inv29[key] : kt.n0inv[key];
   const uint32_t e = kt.rsa_e[key];

@@ -1,7 +1,7 @@
 // Raw RSA PKCS#1 v1.5 verification (include/bftkv_gpu.h: bftkv_gpu_rsa_verify and its key-set forms; rsa_verify_capi.inc).
 //   k_rsav_verify<L,TPI,W>  s^e mod n on mont_mul (mont28.h) and the comparison with the whole encoded message, in one kernel:
 //                           fixed-width signatures and digests in, one verdict and one status byte out
-// Included from capi.hip behind kernels.hip (OP_*, limb_of, RSA_BLOCK).
+// Included from capi.hip behind kernels.hip (OP_*, limb_of, value_limbs, RSA_BLOCK).
 #pragma once
 #include "rsa_verify.h"
 
@@ -57,10 +57,15 @@ __global__ void __launch_bounds__(RSA_BLOCK, 3) k_rsav_verify(uint32_t n_ops, co
   {
     const uint8_t* sp = sigs + (uint64_t)op * nbytes;
     auto sig_b = [&](uint32_t i) -> uint32_t { return i < nbytes ? sp[nbytes - 1 - i] : 0u; };
+    uint32_t x[L];
+    if constexpr (VALUE_LOAD_DWORDS)   // unaligned dwords, all in flight before the first is used (value_load.h)
+      value_limbs<W, L, TPI>(x, nbytes, qlane,
+                             [&](uint32_t o) -> uint32_t { uint32_t w; __builtin_memcpy(&w, sp + o, 4); return w; },
+                             [&](uint32_t o) -> uint32_t { return sp[o]; });
 #pragma unroll
     for (int k = 0; k < L; ++k) {
       const int32_t lo = (qlane * L + k) * W, cut = 8 * (int32_t)kbytes;
-      uint32_t v = limb_of<W>(sig_b, qlane * L + k);
+      uint32_t v = VALUE_LOAD_DWORDS ? x[k] : limb_of<W>(sig_b, qlane * L + k);
       if (lo + W > cut) high |= lo >= cut ? v : v >> (cut - lo);
       if (rule != RSAV_LIVE) v = (qlane == 0 && k == 0) ? 1u : 0u;
       x_lds[k] = v;

@@ -614,42 +614,46 @@ class Context:
         self._check(self.lib.bftkv_gpu_ec_scalar_base_mult(self.h, n, _ptr(sc), f, _ptr(cb), bits, _ptr(out), _ptr(st)), "ec_scalar_base_mult")
         return [out[i].tobytes() for i in range(n)], st[:n]
 
+    def _verdicts(self, label, shape, digests, sigs, slen, key_idx, call, ok=True):
+        """The batched verdict call of every verify method: digests [n_ops] bytes of ONE length and sigs [n_ops] bytes of slen each
+        (else ValueError "label: shape"), key_idx [n_ops] or None; call(n, dg, dlen, sg, ki, valid, st) -> rc, with ki a pointer or
+        None and valid / st the result arrays -> (valid, status), uint8 each."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 1
+        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or not ok or len(sigs) != n:
+            raise ValueError(label + ": " + shape)
+        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
+        self._check(call(n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki), _ptr(valid), _ptr(st)), label)
+        return valid[:n], st[:n]
+
     def ecdsa_verify(self, digests, sigs, keys, curve, key_idx=None):
         """crypto/ecdsa.Verify on raw signatures: digests [n_ops] bytes of ONE length (1..66), sigs [n_ops] bytes r || s (2 fbytes
         each), keys [n_keys] Marshal bytes (1 + 2 fbytes each), key_idx [n_ops] or None (key 0) -> (valid, status), uint8 each."""
         cb, bits, f = _curve_bytes(curve)
-        n = len(digests)
-        dlen = len(digests[0]) if n else 1
-        if any(len(d) != dlen for d in digests) or any(len(s) != 2 * f for s in sigs) or any(len(k) != 1 + 2 * f for k in keys) or len(sigs) != n:
-            raise ValueError("ecdsa_verify: digests of one length, sigs of 2 fbytes, keys of 1 + 2 fbytes")
-        dg, sg, kk = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs)), _u8(b"".join(bytes(k) for k in keys))
-        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
-        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
-        self._check(self.lib.bftkv_gpu_ecdsa_verify(self.h, n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki), len(keys), _ptr(kk),
-                                                    _ptr(cb), bits, _ptr(valid), _ptr(st)), "ecdsa_verify")
-        return valid[:n], st[:n]
+        kk = _u8(b"".join(bytes(k) for k in keys))
+        return self._verdicts("ecdsa_verify", "digests of one length, sigs of 2 fbytes, keys of 1 + 2 fbytes", digests, sigs, 2 * f, key_idx,
+                              lambda n, dg, dlen, sg, ki, valid, st: self.lib.bftkv_gpu_ecdsa_verify(
+                                  self.h, n, dg, dlen, sg, ki, len(keys), _ptr(kk), _ptr(cb), bits, valid, st),
+                              ok=all(len(k) == 1 + 2 * f for k in keys))
 
     def dsa_verify(self, digests, sigs, keys, groups, key_idx=None, pbytes=None, qbytes=None):
         """crypto/dsa.Verify on raw signatures: digests [n_ops] bytes of ONE length (1..64), sigs [n_ops] bytes r || s (2 qbytes each),
         groups [(p, q, g)] ints, keys [(group, y)], key_idx [n_ops] or None (key 0) -> (valid, status), uint8 each.  pbytes / qbytes
         default to the width of the widest p, g, y and to half a signature."""
-        n = len(digests)
-        dlen = len(digests[0]) if n else 1
         if qbytes is None:
-            qbytes = len(sigs[0]) // 2 if n else max((int(g[1]).bit_length() + 7) // 8 for g in groups)
+            qbytes = len(sigs[0]) // 2 if len(digests) else max((int(g[1]).bit_length() + 7) // 8 for g in groups)
         if pbytes is None:
             pbytes = max(1, max((int(v).bit_length() + 7) // 8 for v in [g[0] for g in groups] + [g[2] for g in groups] + [k[1] for k in keys]))
-        if any(len(d) != dlen for d in digests) or any(len(s) != 2 * qbytes for s in sigs) or len(sigs) != n:
-            raise ValueError("dsa_verify: digests of one length, sigs of 2 qbytes")
-        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
-        p, q, g = (_ints_to_be([grp[i] for grp in groups], w) for i, w in ((0, pbytes), (1, qbytes), (2, pbytes)))
-        y = _ints_to_be([k[1] for k in keys], pbytes)
-        kg = np.ascontiguousarray([k[0] for k in keys], dtype=np.uint32)
-        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
-        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
-        self._check(self.lib.bftkv_gpu_dsa_verify(self.h, n, _ptr(dg), dlen, _ptr(sg), qbytes, None if ki is None else _ptr(ki), len(keys), _ptr(y),
-                                                  _ptr(kg), pbytes, len(groups), _ptr(p), _ptr(q), _ptr(g), _ptr(valid), _ptr(st)), "dsa_verify")
-        return valid[:n], st[:n]
+
+        def call(n, dg, dlen, sg, ki, valid, st):
+            p, q, g = (_ints_to_be([grp[i] for grp in groups], w) for i, w in ((0, pbytes), (1, qbytes), (2, pbytes)))
+            y = _ints_to_be([k[1] for k in keys], pbytes)
+            kg = np.ascontiguousarray([k[0] for k in keys], dtype=np.uint32)
+            return self.lib.bftkv_gpu_dsa_verify(self.h, n, dg, dlen, sg, qbytes, ki, len(keys), _ptr(y), _ptr(kg), pbytes, len(groups), _ptr(p), _ptr(q),
+                                                 _ptr(g), valid, st)
+        return self._verdicts("dsa_verify", "digests of one length, sigs of 2 qbytes", digests, sigs, 2 * qbytes, key_idx, call)
 
     def ecdsa_keyset_create(self, keys, curve) -> int:
         """Register keys [n_keys] Marshal bytes (1 + 2 fbytes each) once: Unmarshal's checks and a table per key on the device.
@@ -693,17 +697,8 @@ class Context:
     def ecdsa_verify_keyset(self, keyset: int, digests, sigs, key_idx=None):
         """ecdsa_verify under the keys of a set: digests [n_ops] bytes of ONE length, sigs [n_ops] bytes r || s of the set's curve,
         key_idx [n_ops] into the set or None (key 0) -> (valid, status), uint8 each."""
-        n = len(digests)
-        dlen = len(digests[0]) if n else 1
-        slen = 2 * self._ecdsa_keyset_fbytes(keyset)
-        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or len(sigs) != n:
-            raise ValueError("ecdsa_verify_keyset: digests of one length, sigs of 2 fbytes")
-        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
-        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
-        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
-        self._check(self.lib.bftkv_gpu_ecdsa_verify_keyset(self.h, keyset, n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki),
-                                                           _ptr(valid), _ptr(st)), "ecdsa_verify_keyset")
-        return valid[:n], st[:n]
+        return self._verdicts("ecdsa_verify_keyset", "digests of one length, sigs of 2 fbytes", digests, sigs, 2 * self._ecdsa_keyset_fbytes(keyset), key_idx,
+                              lambda n, dg, dlen, sg, ki, valid, st: self.lib.bftkv_gpu_ecdsa_verify_keyset(self.h, keyset, n, dg, dlen, sg, ki, valid, st))
 
     def selftest_ecdsa_keyset_table(self, keyset: int, key: int) -> np.ndarray:
         """One key's table as the device built it (uint32 words, the layout of ec_field.h fb_table_build)."""
@@ -742,17 +737,8 @@ class Context:
     def dsa_verify_keyset(self, keyset: int, digests, sigs, key_idx=None):
         """dsa_verify under the keys of a set: digests [n_ops] bytes of ONE length (1..64), sigs [n_ops] bytes r || s (2 qbytes of
         the set), key_idx [n_ops] into the set or None (key 0) -> (valid, status), uint8 each."""
-        n = len(digests)
-        dlen = len(digests[0]) if n else 1
-        slen = 2 * self.dsa_keyset_info(keyset)["qbytes"]
-        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or len(sigs) != n:
-            raise ValueError("dsa_verify_keyset: digests of one length, sigs of 2 qbytes")
-        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
-        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
-        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
-        self._check(self.lib.bftkv_gpu_dsa_verify_keyset(self.h, keyset, n, _ptr(dg), dlen, _ptr(sg), None if ki is None else _ptr(ki),
-                                                         _ptr(valid), _ptr(st)), "dsa_verify_keyset")
-        return valid[:n], st[:n]
+        return self._verdicts("dsa_verify_keyset", "digests of one length, sigs of 2 qbytes", digests, sigs, 2 * self.dsa_keyset_info(keyset)["qbytes"], key_idx,
+                              lambda n, dg, dlen, sg, ki, valid, st: self.lib.bftkv_gpu_dsa_verify_keyset(self.h, keyset, n, dg, dlen, sg, ki, valid, st))
 
     def selftest_dsa_keyset_table(self, keyset: int, base: int) -> np.ndarray:
         """One base's table as the device built it (the groups' g first, then the keys' y): uint32 [windows][2^w - 1][76]."""
@@ -766,20 +752,14 @@ class Context:
         """rsa.VerifyPKCS1v15 on raw signatures: digests [n_ops] bytes of ONE length (the size of hash_id's hash; 1..64 for hash_id
         0, no prefix), sigs [n_ops] bytes of nbytes each, keys [(n, e)] ints, key_idx [n_ops] or None (key 0) -> (valid, status),
         uint8 each.  nbytes defaults to the length of a signature, or to the widest modulus."""
-        n = len(digests)
-        dlen = len(digests[0]) if n else 1
         if nbytes is None:
-            nbytes = len(sigs[0]) if n else max(1, max((int(k[0]).bit_length() + 7) // 8 for k in keys))
-        if any(len(d) != dlen for d in digests) or any(len(s) != nbytes for s in sigs) or len(sigs) != n:
-            raise ValueError("rsa_verify: digests of one length, sigs of nbytes")
-        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
-        kn = _ints_to_be([k[0] for k in keys], nbytes)
-        ke = np.ascontiguousarray([k[1] for k in keys], dtype=np.uint32)
-        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
-        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
-        self._check(self.lib.bftkv_gpu_rsa_verify(self.h, n, _ptr(dg), hash_id, dlen, _ptr(sg), nbytes, None if ki is None else _ptr(ki), len(keys),
-                                                  _ptr(kn), _ptr(ke), _ptr(valid), _ptr(st)), "rsa_verify")
-        return valid[:n], st[:n]
+            nbytes = len(sigs[0]) if len(digests) else max(1, max((int(k[0]).bit_length() + 7) // 8 for k in keys))
+
+        def call(n, dg, dlen, sg, ki, valid, st):
+            kn = _ints_to_be([k[0] for k in keys], nbytes)
+            ke = np.ascontiguousarray([k[1] for k in keys], dtype=np.uint32)
+            return self.lib.bftkv_gpu_rsa_verify(self.h, n, dg, hash_id, dlen, sg, nbytes, ki, len(keys), _ptr(kn), _ptr(ke), valid, st)
+        return self._verdicts("rsa_verify", "digests of one length, sigs of nbytes", digests, sigs, nbytes, key_idx, call)
 
     def rsa_keyset_create(self, keys, nbytes=None) -> int:
         """Register keys [(n, e)] ints once: their Montgomery rows stay on the device.  An even modulus does not refuse the set
@@ -804,17 +784,8 @@ class Context:
     def rsa_verify_keyset(self, keyset: int, digests, sigs, hash_id: int, key_idx=None):
         """rsa_verify under the keys of a set: digests [n_ops] bytes of ONE length, sigs [n_ops] bytes of the set's nbytes, key_idx
         [n_ops] into the set or None (key 0) -> (valid, status), uint8 each."""
-        n = len(digests)
-        dlen = len(digests[0]) if n else 1
-        slen = self.rsa_keyset_info(keyset)["nbytes"]
-        if any(len(d) != dlen for d in digests) or any(len(s) != slen for s in sigs) or len(sigs) != n:
-            raise ValueError("rsa_verify_keyset: digests of one length, sigs of the set's nbytes")
-        dg, sg = _u8(b"".join(bytes(d) for d in digests)), _u8(b"".join(bytes(s) for s in sigs))
-        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
-        valid, st = np.zeros(n + 8, dtype=np.uint8), np.zeros(n + 8, dtype=np.uint8)
-        self._check(self.lib.bftkv_gpu_rsa_verify_keyset(self.h, keyset, n, _ptr(dg), hash_id, dlen, _ptr(sg), None if ki is None else _ptr(ki),
-                                                         _ptr(valid), _ptr(st)), "rsa_verify_keyset")
-        return valid[:n], st[:n]
+        return self._verdicts("rsa_verify_keyset", "digests of one length, sigs of the set's nbytes", digests, sigs, self.rsa_keyset_info(keyset)["nbytes"], key_idx,
+                              lambda n, dg, dlen, sg, ki, valid, st: self.lib.bftkv_gpu_rsa_verify_keyset(self.h, keyset, n, dg, hash_id, dlen, sg, ki, valid, st))
 
 
 class Batcher:
@@ -957,23 +928,26 @@ class Batcher:
                                                    _ptr(valid), _ptr(st))
         return rc, int(st[0]), int(valid[0])
 
+    def _verdict(self, digest: bytes, sig: bytes, call):
+        """One signature against a resident key set: call(dg, dlen, sg, valid, st) -> rc; -> (rc, status, valid)."""
+        dg, sg = _u8(digest), _u8(sig)
+        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = call(_ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
+        return rc, int(st[0]), int(valid[0])
+
     def ecdsa_verify_keyset(self, keyset: int, key: int, digest: bytes, sig: bytes):
         """crypto/ecdsa.Verify for one raw signature r || s under key `key` of a resident key set -> (rc, status, valid)."""
         if not digest or len(sig) != 2 * self.ctx._ecdsa_keyset_fbytes(keyset):
             raise ValueError("ecdsa_verify_keyset: sig of 2 fbytes of the set's curve, a non-empty digest")
-        dg, sg = _u8(digest), _u8(sig)
-        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
-        rc = self.lib.bftkv_gpu_batcher_ecdsa_verify_keyset(self.h, keyset, key, _ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
-        return rc, int(st[0]), int(valid[0])
+        return self._verdict(digest, sig, lambda dg, dlen, sg, valid, st: self.lib.bftkv_gpu_batcher_ecdsa_verify_keyset(
+            self.h, keyset, key, dg, dlen, sg, valid, st))
 
     def dsa_verify_keyset(self, keyset: int, key: int, digest: bytes, sig: bytes):
         """crypto/dsa.Verify for one raw signature r || s under key `key` of a resident DSA key set -> (rc, status, valid)."""
         if not digest or len(sig) != 2 * self.ctx.dsa_keyset_info(keyset)["qbytes"]:
             raise ValueError("dsa_verify_keyset: sig of 2 qbytes of the set, a non-empty digest")
-        dg, sg = _u8(digest), _u8(sig)
-        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
-        rc = self.lib.bftkv_gpu_batcher_dsa_verify_keyset(self.h, keyset, key, _ptr(dg), len(digest), _ptr(sg), _ptr(valid), _ptr(st))
-        return rc, int(st[0]), int(valid[0])
+        return self._verdict(digest, sig, lambda dg, dlen, sg, valid, st: self.lib.bftkv_gpu_batcher_dsa_verify_keyset(
+            self.h, keyset, key, dg, dlen, sg, valid, st))
 
     def rsa_verify(self, digest: bytes, sig: bytes, n: int, e: int, hash_id: int):
         """rsa.VerifyPKCS1v15 for one raw signature (nbytes = len(sig)) under (n, e) -> (rc, status, valid)."""
@@ -988,10 +962,8 @@ class Batcher:
         """rsa.VerifyPKCS1v15 for one raw signature under key `key` of a resident RSA key set -> (rc, status, valid)."""
         if not digest or len(sig) != self.ctx.rsa_keyset_info(keyset)["nbytes"]:
             raise ValueError("rsa_verify_keyset: sig of the set's nbytes, a non-empty digest")
-        dg, sg = _u8(digest), _u8(sig)
-        valid, st = np.full(1, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
-        rc = self.lib.bftkv_gpu_batcher_rsa_verify_keyset(self.h, keyset, key, _ptr(dg), hash_id, len(digest), _ptr(sg), _ptr(valid), _ptr(st))
-        return rc, int(st[0]), int(valid[0])
+        return self._verdict(digest, sig, lambda dg, dlen, sg, valid, st: self.lib.bftkv_gpu_batcher_rsa_verify_keyset(
+            self.h, keyset, key, dg, hash_id, dlen, sg, valid, st))
 
     def modexp(self, base: int, exp: int, mod: int, nbytes: int = 256, exp_len: int = 32):
         """base^exp mod `mod` (CalculatePartialR dsa.go:27-31; the per-fragment power of rsa.go:161-171)."""

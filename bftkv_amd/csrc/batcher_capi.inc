@@ -544,14 +544,14 @@ struct bftkv_gpu_batcher {
     publish_verdicts(g, rc, st.data(), valid.data());
   }
 
-  // EcdsaVerifyKeyset, DsaVerifyKeyset.  sig_bytes(ctx, handle): the bytes of one r || s under the set, 0 if there is no such set;
+  // EcdsaVerifyKeyset, DsaVerifyKeyset, RsaVerifyKeyset.  Set: the kind's key set, which tells the bytes of one signature under it;
   // verify: the kind's batched impl.  The lane holds its hold on the root's tables from the look at the set to the end of the device
   // call, so the set cannot be replaced by one of another signature length in between.  The signature bytes of every caller are
   // copied with the length taken from the set found NOW: a caller that retired the set while this request waited, and let a wider set
   // take the handle, has broken the rule in include/bftkv_gpu.h (no destroy while calls naming the set are in flight) and the copy
   // reads past its buffer.
-  template <typename SigBytes, typename Verify>
-  void run_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls, SigBytes sig_bytes, Verify verify) {
+  template <typename Set, typename Verify>
+  void run_verify_keyset(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls, Verify verify) {
     const Req& r0 = *g[0];
     const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k;
     std::vector<uint8_t> valid(n, 0), st((size_t)n + 8, BFTKV_TH_FAILED);
@@ -559,7 +559,8 @@ struct bftkv_gpu_batcher {
     {
       ctx_lock lk(lane.ctx->mu);
       KtRead kr(lane.ctx);
-      const size_t sw = kr.rc ? 0 : sig_bytes(lane.ctx, r0.quorum);
+      const Set* ks = kr.rc ? nullptr : KeySets<Set>::find(lane.ctx, r0.quorum);
+      const size_t sw = ks ? ks->sig_bytes() : 0;
       if (kr.rc) rc = kr.rc;
       else if (!sw) rc = BFTKV_E_INVALID;
       else {
@@ -705,26 +706,19 @@ struct bftkv_gpu_batcher {
         case Kind::EcdsaCalculateR: run_ecdsa(lane, g, calls); break;
         case Kind::EcdsaVerify: run_ecdsa_verify(lane, g, calls); break;
         case Kind::EcdsaVerifyKeyset:
-          run_verify_keyset(lane, g, calls, [](const bftkv_gpu_ctx* c, int set) {
-            const EcKeySet* ks = ec_keyset_find(c, set);
-            return ks ? 2 * (size_t)((ks->bits + 7) / 8) : 0;
-          }, ecdsa_verify_keyset_impl);
+          run_verify_keyset<EcKeySet>(lane, g, calls, ecdsa_verify_keyset_impl);
           break;
         case Kind::DsaVerify: run_dsa_verify(lane, g, calls); break;
         case Kind::DsaVerifyKeyset:
-          run_verify_keyset(lane, g, calls, [](const bftkv_gpu_ctx* c, int set) {
-            const DsaKeySet* ks = dsa_keyset_find(c, set);
-            return ks ? 2 * (size_t)ks->qbytes : 0;
-          }, dsa_verify_keyset_impl);
+          run_verify_keyset<DsaKeySet>(lane, g, calls, dsa_verify_keyset_impl);
           break;
         case Kind::RsaVerify: run_rsa_verify(lane, g, calls); break;
         case Kind::RsaVerifyKeyset: {
           const uint32_t hash_id = g[0]->th_qbytes;
-          run_verify_keyset(lane, g, calls, [](const bftkv_gpu_ctx* c, int set) {
-            const RsaKeySet* ks = rsa_keyset_find(c, set);
-            return ks ? (size_t)ks->nbytes : 0;
-          }, [hash_id](bftkv_gpu_ctx* c, int set, uint32_t n, const uint8_t* dg, uint32_t dlen, const uint8_t* sg, const uint32_t* idx, uint8_t* valid,
-                       uint8_t* st, bool dev) { return rsa_verify_keyset_impl(c, set, n, dg, hash_id, dlen, sg, idx, valid, st, dev); });
+          run_verify_keyset<RsaKeySet>(lane, g, calls, [hash_id](bftkv_gpu_ctx* c, int set, uint32_t n, const uint8_t* dg, uint32_t dlen, const uint8_t* sg,
+                                                                 const uint32_t* idx, uint8_t* valid, uint8_t* st, bool dev) {
+            return rsa_verify_keyset_impl(c, set, n, dg, hash_id, dlen, sg, idx, valid, st, dev);
+          });
           break;
         }
       }

@@ -26,6 +26,7 @@
 #include <shared_mutex>
 #include <system_error>
 #include <thread>
+#include <tuple>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -94,8 +95,22 @@ struct QuorumHost {
   uint32_t ids_off[MAX_QC + 1];
 };
 
+// A key set's own copy of the Montgomery rows of its moduli (n, R^2 mod n and -n^-1 per row; R_wide^2 mod n as well where the set's
+// kernels read it), copied out of the context's cache, which may drop them: no call on the set uploads anything.
+struct ModRows {
+  DevBuf b[4];
+  ModTab view() const { return ModTab{b[0].as<uint32_t>(), b[1].as<uint32_t>(), b[2].as<uint32_t>(), b[3].as<uint32_t>()}; }
+  template <typename Set>                  // (the kind of the set that keeps the rows: it names the failure)
+  int copy_from(bftkv_gpu_ctx* c, const ModTab& src, size_t n_rows, bool with_wide);
+  void release() { for (DevBuf& x : b) x.release(); }
+};
+
+// The resident key sets.  Every kind has `live`, release(), its name in messages (`kind`) and the bytes of one signature under
+// the set (sig_bytes); KeySets<Set> below keeps the handles of a kind.
+
 // A resident ECDSA key set (ec_capi.inc): one fixed-base table per key, built on the device at registration
 struct EcKeySet {
+  static constexpr const char* kind = "ECDSA";
   bool live = false;
   int curve_id = -1;                       // index into kEcCurves
   uint32_t bits = 0, n_keys = 0, n_refused = 0;
@@ -104,30 +119,34 @@ struct EcKeySet {
   std::vector<uint8_t> curve;              // P || N || B || Gx || Gy
   DevBuf tab;                              // [n_keys][key_words]; the rows of a refused key are zero
   DevBuf refused;                          // [n_keys] bytes: 1 = elliptic.Unmarshal refuses the key
-  DevBuf mod[4];                           // N as a ModTab for k_modinv (the set's own copy: no call uploads anything)
-  void release() { tab.release(); refused.release(); for (DevBuf& b : mod) b.release(); }
+  ModRows mod;                             // N for k_modinv, with the wide row
+  size_t sig_bytes() const { return 2 * (size_t)((bits + 7) / 8); }
+  void release() { tab.release(); refused.release(); mod.release(); }
 };
 
 // A resident DSA key set (dsa_keyset_capi.inc): one fixed-base window table per distinct base, the groups' g first, then the keys' y
 struct DsaKeySet {
+  static constexpr const char* kind = "DSA";
   bool live = false;
   uint32_t n_keys = 0, n_groups = 0, pbytes = 0, qbytes = 0;
   uint32_t w = 0, windows = 0;             // window bits and ceil(max bits(q) / w)
   DevBuf tab;                              // [n_groups + n_keys][windows][2^w - 1][76], fully reduced Montgomery entries (R = 2^2128)
-  DevBuf modp[3], modq[3];                 // n, R^2, -n^-1 rows of every p and q (the set's own copies: no call uploads anything)
+  ModRows modp, modq;                      // every p and q
   DevBuf q_be, key_group;                  // [n_groups][qbytes] bytes; [n_keys] clamped group indices
   uint64_t table_bytes() const { return (uint64_t)(n_groups + n_keys) * windows * ((1u << w) - 1u) * MONT_N * 4; }
-  static ModTab rows(const DevBuf (&m)[3]) { return ModTab{m[0].as<uint32_t>(), m[1].as<uint32_t>(), m[2].as<uint32_t>(), nullptr}; }      // rows(modp), rows(modq)
-  void release() { tab.release(); q_be.release(); key_group.release(); for (DevBuf& b : modp) b.release(); for (DevBuf& b : modq) b.release(); }
+  size_t sig_bytes() const { return 2 * (size_t)qbytes; }
+  void release() { tab.release(); q_be.release(); key_group.release(); modp.release(); modq.release(); }
 };
 
 // A resident RSA key set (rsa_verify_capi.inc): the keys' Montgomery rows in both forms of k_rsav_verify.  An even modulus has
 // zero rows and is counted in n_refused.
 struct RsaKeySet {
+  static constexpr const char* kind = "RSA";
   bool live = false;
   uint32_t n_keys = 0, n_refused = 0, nbytes = 0;
   DevBuf n29, r2_29, n80, r2_80;           // [n_keys][72] limbs of 29 bits (R = 2^2088); [n_keys][80] limbs of 28 bits (R = 2^2240)
   DevBuf meta;                             // [n_keys] uint4: -n^-1 mod 2^29, k = ceil(bits(n) / 8), e, 1 for an even n
+  size_t sig_bytes() const { return nbytes; }
   void release() { n29.release(); r2_29.release(); n80.release(); r2_80.release(); meta.release(); }
 };
 
@@ -186,9 +205,8 @@ struct bftkv_gpu_ctx {
   KeyTableDev kt{};
 
   std::vector<QuorumHost> quorums;
-  std::vector<EcKeySet> ec_keysets;    // root: the handles of bftkv_gpu_ecdsa_keyset_create; forks read them under KtRead, without a copy
-  std::vector<DsaKeySet> dsa_keysets;  // root: the handles of bftkv_gpu_dsa_keyset_create (a space of their own), read the same way
-  std::vector<RsaKeySet> rsa_keysets;  // root: the handles of bftkv_gpu_rsa_keyset_create (a space of their own), read the same way
+  // root: the handles of bftkv_gpu_{ecdsa,dsa,rsa}_keyset_create, a space per kind; forks read them under KtRead, without a copy (KeySets)
+  std::tuple<std::vector<EcKeySet>, std::vector<DsaKeySet>, std::vector<RsaKeySet>> keysets;
 
   // per-call arena
   DevBuf txt_mid32, txt_mid64, txt_tail, txt_len;     // text-mode hashing state (TextDev)
@@ -280,7 +298,7 @@ namespace {
 
 int fork_refresh(bftkv_gpu_ctx* c);
 
-// Exclusive access to the key table / quorum descriptors / ECDSA and DSA key sets of a root context (see bftkv_gpu_ctx::root).
+// Exclusive access to the key table / quorum descriptors / key sets (KeySets) of a root context (see bftkv_gpu_ctx::root).
 struct KtWrite {
   bftkv_gpu_ctx* c;
   explicit KtWrite(bftkv_gpu_ctx* c_) : c(c_) { c->kt_writers.fetch_add(1); c->kt_rw.lock(); }
@@ -362,6 +380,71 @@ int fail(bftkv_gpu_ctx* c, int rc, const char* what, hipError_t e = hipSuccess) 
     hipError_t _e = (call);                                                \
     if (_e != hipSuccess) return fail((c), BFTKV_E_DEVICE, #call, _e);     \
   } while (0)
+
+// The handles of one kind of resident key set (EcKeySet, DsaKeySet, RsaKeySet; a handle space per kind: handle 0 of one kind has
+// nothing to do with handle 0 of another).  Sets live on the ROOT context like quorums: made and retired there under KtWrite (the
+// forks' calls in flight drain first), read by the forks under KtRead without a copy.  Every entry below is called with c->mu held.
+template <typename Set>
+struct KeySets {
+  // caller holds, on a fork, the root's key-table lock (KtRead) for as long as it uses the set
+  static const Set* find(const bftkv_gpu_ctx* c, int h) {
+    const std::vector<Set>& keysets = std::get<std::vector<Set>>((c->root ? c->root : c)->keysets);
+    return h >= 0 && (size_t)h < keysets.size() && keysets[h].live ? &keysets[h] : nullptr;
+  }
+  static int bad_handle(bftkv_gpu_ctx* c) { return fail(c, BFTKV_E_INVALID, (std::string("bad ") + Set::kind + " key set handle").c_str()); }
+  static int nomem(bftkv_gpu_ctx* c) {
+    (void)hipGetLastError();
+    return fail(c, BFTKV_E_NOMEM, (std::string(Set::kind) + " key set: device allocation failed").c_str());
+  }
+  // build(Set&) fills a new set on c->stream.  A failed build leaves nothing behind: whatever it queued on the set's buffers (copies,
+  // memsets, table kernels) is drained, THEN they are freed.  A built set takes the lowest dead handle, or a new one.
+  template <typename Build>
+  static int create(bftkv_gpu_ctx* c, int* handle_out, Build&& build) {
+    if (c->root) return fail(c, BFTKV_E_STATE, (std::string(Set::kind) + " key sets are created on the root context; its forks see them").c_str());
+    HIPCHK(c, hipSetDevice(c->device));
+    Set ks;
+    if (const int rc = build(ks)) {
+      (void)hipStreamSynchronize(c->stream);
+      ks.release();
+      return rc;
+    }
+    ks.live = true;
+    std::vector<Set>& all = std::get<std::vector<Set>>(c->keysets);
+    auto slot = std::find_if(all.begin(), all.end(), [](const Set& s) { return !s.live; });
+    KtWrite kw(c);
+    if (slot == all.end()) slot = all.emplace(all.end());
+    *slot = std::move(ks);
+    *handle_out = (int)(slot - all.begin());
+    return 0;
+  }
+  static int retire(bftkv_gpu_ctx* c, int h) {
+    if (c->root) return fail(c, BFTKV_E_STATE, (std::string(Set::kind) + " key sets are destroyed on the root context").c_str());
+    if (!find(c, h)) return bad_handle(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    KtWrite kw(c);
+    HIPCHK(c, hipDeviceSynchronize());          // (_dev calls return before their kernels have run: nothing may still read the set)
+    Set& ks = std::get<std::vector<Set>>(c->keysets)[h];
+    ks.release();
+    ks = Set();
+    return 0;
+  }
+};
+// bftkv_gpu_destroy
+void keysets_release_all(bftkv_gpu_ctx* c) {
+  std::apply([](auto&... of_kind) { (std::for_each(of_kind.begin(), of_kind.end(), [](auto& ks) { ks.release(); }), ...); }, c->keysets);
+}
+
+template <typename Set>
+int ModRows::copy_from(bftkv_gpu_ctx* c, const ModTab& src, size_t n_rows, bool with_wide) {
+  const void* from[4] = {src.n_limbs, src.r2_limbs, src.n0inv, src.r2w_limbs};
+  const size_t len[4] = {n_rows * MONT_N * 4, n_rows * MONT_N * 4, n_rows * 4, n_rows * MONT_N_WIDE * 4};
+  for (int k = 0; k < (with_wide ? 4 : 3); ++k) {
+    // (the one-row form with the wide row keeps ensure()'s slack, the per-group form is exact: as each was before they met here)
+    if ((with_wide ? b[k].ensure(len[k]) : b[k].ensure_exact(len[k])) != hipSuccess) return KeySets<Set>::nomem(c);
+    HIPCHK(c, hipMemcpyAsync(b[k].p, from[k], len[k], hipMemcpyDeviceToDevice, c->stream));
+  }
+  return 0;
+}
 
 template <typename T>
 int upload(bftkv_gpu_ctx* c, DevBuf& b, const std::vector<T>& v) {
@@ -1304,9 +1387,7 @@ void bftkv_gpu_destroy(bftkv_gpu_ctx* c) {
                     &c->in_ss, &c->in_ss_off, &c->in_prefix, &c->in_prefix_off, &c->in_shared, &c->in_shared_off, &c->in_seg, &c->st_tmp, &c->item_tmp, &c->bits_tmp, &c->plan_cut, &c->txt_mid32, &c->txt_mid64, &c->txt_tail, &c->txt_len})
     b->release();
   for (auto& q : c->quorums) { q.member.release(); q.ids.release(); }
-  for (EcKeySet& ks : c->ec_keysets) ks.release();
-  for (DsaKeySet& ks : c->dsa_keysets) ks.release();
-  for (RsaKeySet& ks : c->rsa_keysets) ks.release();
+  keysets_release_all(c);
   c->in_pack.release();
   c->forced_iss.release();
   release_small_pin(c);

@@ -7,13 +7,6 @@ namespace {
 
 constexpr uint32_t DSA_KEYSET_MAX_KEYS = 4096, DSA_KEYSET_MAX_GROUPS = 4096;
 
-// caller holds c->mu and, on a fork, the root's key-table lock (KtRead)
-const DsaKeySet* dsa_keyset_find(const bftkv_gpu_ctx* c, int keyset) {
-  const bftkv_gpu_ctx* r = c->root ? c->root : c;
-  if (keyset < 0 || (size_t)keyset >= r->dsa_keysets.size() || !r->dsa_keysets[keyset].live) return nullptr;
-  return &r->dsa_keysets[keyset];
-}
-
 // chains of at most 256 entries: one part up to 8-bit windows, 2^(w - 8) beyond (k_dsav_comb_build)
 inline uint32_t dsa_keyset_parts(uint32_t w) { return w > 8 ? 1u << (w - 8) : 1u; }
 
@@ -23,33 +16,21 @@ int dsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* key
       pbytes == 0 || pbytes > 256 || qbytes == 0 || qbytes > 32 || (window_bits != 0 && (window_bits < DSAV_COMB_WMIN || window_bits > DSAV_COMB_WMAX)))
     return BFTKV_E_INVALID;
   ctx_lock lk(c->mu);
-  if (c->root) return fail(c, BFTKV_E_STATE, "DSA key sets are created on the root context; its forks see them");
-  HIPCHK(c, hipSetDevice(c->device));
-  ScratchBufs sb(c);
-  { int grc = modtab_gc(c); if (grc) return grc; }
-  DsaKeySet ks;
-  int rc = 0;
-  auto nomem = [&]() { (void)hipGetLastError(); return fail(c, BFTKV_E_NOMEM, "DSA key set: device allocation failed"); };
-  auto build = [&]() -> int {
+  return KeySets<DsaKeySet>::create(c, keyset_out, [&](DsaKeySet& ks) -> int {
+    ScratchBufs sb(c);
+    { int grc = modtab_gc(c); if (grc) return grc; }
+    int rc = 0;
     ks.n_keys = n_keys; ks.n_groups = n_groups; ks.pbytes = pbytes; ks.qbytes = qbytes;
     ks.w = window_bits ? window_bits : DSAV_COMB_WDEF;
     const DsaBases hb(n_keys, keys_y, key_group, pbytes, n_groups, q, qbytes, g);
     ks.windows = dsav_comb_windows(hb.max_qbits, ks.w);
-    // the rows of every p and q, copied out of the context's cache (which may drop them) into the set
-    ModTab mp, mq;
+    ModTab mp, mq;                                                               // the rows of every p and q
     if ((rc = make_modtab(c, sb, p, n_groups, pbytes, &mp))) return rc;          // (an even p or q: BFTKV_E_UNSUPPORTED, no set)
     if ((rc = make_modtab(c, sb, q, n_groups, qbytes, &mq))) return rc;
-    const size_t len[3] = {(size_t)n_groups * MONT_N * 4, (size_t)n_groups * MONT_N * 4, (size_t)n_groups * 4};
-    const void* srcp[3] = {mp.n_limbs, mp.r2_limbs, mp.n0inv};
-    const void* srcq[3] = {mq.n_limbs, mq.r2_limbs, mq.n0inv};
-    for (int k = 0; k < 3; ++k) {
-      if (ks.modp[k].ensure_exact(len[k]) != hipSuccess || ks.modq[k].ensure_exact(len[k]) != hipSuccess) return nomem();
-      HIPCHK(c, hipMemcpyAsync(ks.modp[k].p, srcp[k], len[k], hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(ks.modq[k].p, srcq[k], len[k], hipMemcpyDeviceToDevice, c->stream));
-    }
+    if ((rc = ks.modp.copy_from<DsaKeySet>(c, mp, n_groups, false)) || (rc = ks.modq.copy_from<DsaKeySet>(c, mq, n_groups, false))) return rc;
     if (ks.q_be.ensure_exact((size_t)n_groups * qbytes) != hipSuccess || ks.key_group.ensure_exact((size_t)n_keys * 4) != hipSuccess ||
         ks.tab.ensure_exact(ks.table_bytes()) != hipSuccess)
-      return nomem();
+      return KeySets<DsaKeySet>::nomem(c);
     HIPCHK(c, hipMemcpyAsync(ks.q_be.p, q, (size_t)n_groups * qbytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(ks.key_group.p, hb.key_group.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, c->stream));
     // the bases as one array of limbs (scratch of this call)
@@ -58,34 +39,17 @@ int dsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* key
     if ((rc = to_dev_limbs(c, sb, hb.bases.data(), n_bases, pbytes, &d_bases))) return rc;
     const uint32_t parts = dsa_keyset_parts(ks.w);
     hipLaunchKernelGGL((k_dsav_comb_build<MONT_L, MONT_TPI>), quad_grid(n_bases * ks.windows * parts), dim3(RSA_BLOCK), 0, c->stream, n_groups, n_keys,
-                       (const uint32_t*)d_bases, ks.key_group.as<uint32_t>(), ks.rows(ks.modp), ks.w, ks.windows, parts, ks.tab.as<uint32_t>());
+                       (const uint32_t*)d_bases, ks.key_group.as<uint32_t>(), ks.modp.view(), ks.w, ks.windows, parts, ks.tab.as<uint32_t>());
     HIPCHK(c, hipStreamSynchronize(c->stream));          // (the host vectors above die with this call)
     HIPCHK(c, hipGetLastError());
     return 0;
-  };
-  rc = build();
-  if (rc) { (void)hipStreamSynchronize(c->stream); ks.release(); return rc; }
-  ks.live = true;
-  int h = -1;
-  for (size_t i = 0; i < c->dsa_keysets.size(); ++i) if (!c->dsa_keysets[i].live) { h = (int)i; break; }
-  KtWrite kw(c);
-  if (h < 0) { c->dsa_keysets.emplace_back(); h = (int)c->dsa_keysets.size() - 1; }
-  c->dsa_keysets[h] = std::move(ks);
-  *keyset_out = h;
-  return 0;
+  });
 }
 
 int dsa_keyset_destroy_impl(bftkv_gpu_ctx* c, int keyset) {
   if (!c) return BFTKV_E_INVALID;
   ctx_lock lk(c->mu);
-  if (c->root) return fail(c, BFTKV_E_STATE, "DSA key sets are destroyed on the root context");
-  if (!dsa_keyset_find(c, keyset)) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
-  HIPCHK(c, hipSetDevice(c->device));
-  KtWrite kw(c);
-  HIPCHK(c, hipDeviceSynchronize());          // (_dev calls return before their kernels have run: nothing may still read the tables)
-  c->dsa_keysets[keyset].release();
-  c->dsa_keysets[keyset] = DsaKeySet();
-  return 0;
+  return KeySets<DsaKeySet>::retire(c, keyset);
 }
 
 int dsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_groups_out, uint32_t* pbytes_out, uint32_t* qbytes_out,
@@ -94,8 +58,8 @@ int dsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uin
   ctx_lock lk(c->mu);
   KtRead kr(c);
   if (kr.rc) return kr.rc;
-  const DsaKeySet* ks = dsa_keyset_find(c, keyset);
-  if (!ks) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
+  const DsaKeySet* ks = KeySets<DsaKeySet>::find(c, keyset);
+  if (!ks) return KeySets<DsaKeySet>::bad_handle(c);
   if (n_keys_out) *n_keys_out = ks->n_keys;
   if (n_groups_out) *n_groups_out = ks->n_groups;
   if (pbytes_out) *pbytes_out = ks->pbytes;
@@ -112,7 +76,7 @@ int dsa_keyset_table_impl(bftkv_gpu_ctx* c, int keyset, uint32_t base, uint32_t*
   ctx_lock lk(c->mu);
   KtRead kr(c);
   if (kr.rc) return kr.rc;
-  const DsaKeySet* ks = dsa_keyset_find(c, keyset);
+  const DsaKeySet* ks = KeySets<DsaKeySet>::find(c, keyset);
   if (!ks || base >= ks->n_groups + ks->n_keys) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle or base index");
   const uint64_t words = ks->table_bytes() / 4 / (ks->n_groups + ks->n_keys);
   if (cap_words < words) return fail(c, BFTKV_E_NOMEM, "words_out holds less than one table");
@@ -126,25 +90,16 @@ int dsa_keyset_table_impl(bftkv_gpu_ctx* c, int keyset, uint32_t base, uint32_t*
 // form's own arrays (the rows, the orders, the groups and the tables are resident), so the device form never waits.
 int dsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
                            const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out, bool dev) {
-  if (!c || n_ops > DSAV_MAX_OPS || (n_ops && (!valid_out || !status_out))) return BFTKV_E_INVALID;
-  ctx_lock lk(c->mu);
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  VerdictOut vo{valid_out, status_out, n_ops, dev};
-  if ((rc = vo.fail_closed(c))) return rc;
-  if (dlen == 0 || dlen > 64 || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
-  KtRead kr(c);
-  if (kr.rc) return kr.rc;
-  const DsaKeySet* ks = dsa_keyset_find(c, keyset);
-  if (!ks) return fail(c, BFTKV_E_INVALID, "bad DSA key set handle");
-  if (n_ops == 0) return 0;
-  ScratchBufs sb(c);
-  DsavScratch w;
-  if ((rc = dsav_prep(c, sb, vo, digests, dlen, sigs, ks->qbytes, key_idx, ks->n_keys, ks->key_group.as<uint32_t>(), ks->q_be.as<uint8_t>(), &w))) return rc;
-  hipLaunchKernelGGL((k_dsav_comb_exp<MONT_L, MONT_TPI>), quad_grid(n_ops), dim3(RSA_BLOCK), 0, c->stream, n_ops, (const uint32_t*)w.e, (const uint32_t*)w.ok,
-                     (const uint32_t*)w.og, (const uint8_t*)w.flag, ks->n_groups, ks->rows(ks->modp), ks->rows(ks->modq), ks->tab.as<uint32_t>(), ks->w,
-                     ks->windows, (uint8_t*)vo.d_valid);
-  return vo.finish(c);
+  const bool shape_ok = dlen != 0 && dlen <= 64 && (!n_ops || (digests && sigs));
+  return verify_on_keyset<DsaKeySet>(c, keyset, n_ops, DSAV_MAX_OPS, valid_out, status_out, dev, shape_ok, [&](const DsaKeySet& ks, VerdictOut& vo) -> int {
+    ScratchBufs sb(c);
+    DsavScratch w;
+    if (int rc = dsav_prep(c, sb, vo, digests, dlen, sigs, ks.qbytes, key_idx, ks.n_keys, ks.key_group.as<uint32_t>(), ks.q_be.as<uint8_t>(), &w)) return rc;
+    hipLaunchKernelGGL((k_dsav_comb_exp<MONT_L, MONT_TPI>), quad_grid(n_ops), dim3(RSA_BLOCK), 0, c->stream, n_ops, (const uint32_t*)w.e, (const uint32_t*)w.ok,
+                       (const uint32_t*)w.og, (const uint8_t*)w.flag, ks.n_groups, ks.modp.view(), ks.modq.view(), ks.tab.as<uint32_t>(), ks.w, ks.windows,
+                       (uint8_t*)vo.d_valid);
+    return vo.finish(c);
+  });
 }
 
 }  // namespace

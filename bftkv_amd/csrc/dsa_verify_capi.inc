@@ -73,10 +73,8 @@ int dsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, ui
   if ((rc = dev_alloc(c, sb, (size_t)n_bases * MULTIEXP_ENT * MONT_N * 4, &d_tab, false))) return rc;
   if ((rc = dsav_prep(c, sb, vo, digests, dlen, sigs, qbytes, key_idx, n_keys, d_kg, d_q, &w))) return rc;
   hipStream_t s = c->stream;
-  // lanes per number as for k_multiexp: 8 while the signatures leave at most one wave per SIMD, else 4 (BFTKV_MULTIEXP_LANES
-  // overrides).  The tables take the form of the exponentiation that reads them.
-  const bool wide = c->multiexp_lanes ? c->multiexp_lanes == 8 : (uint64_t)n_ops * MULTI_TPI8 <= (uint64_t)c->n_cus * 4 * 64;
-  if (wide) {
+  // lanes per number as for k_multiexp (BFTKV_MULTIEXP_LANES overrides).  The tables take the form of the exponentiation that reads them.
+  if (lanes_wide(c, c->multiexp_lanes, n_ops)) {
     constexpr uint32_t G = RSA_BLOCK / MULTI_TPI8;
     hipLaunchKernelGGL((k_dsav_tables<MULTI_L8, MULTI_TPI8>), dim3((n_bases + G - 1) / G), dim3(RSA_BLOCK), 0, s, n_groups, n_keys, (const uint32_t*)d_bases,
                        (const uint32_t*)d_kg, mp, (uint32_t*)d_tab);

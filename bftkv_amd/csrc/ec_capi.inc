@@ -99,6 +99,27 @@ struct VerdictOut {
   }
 };
 
+// The head of a verification against a resident key set, for every kind.  In this order: what is refused before the lock leaves the
+// caller's arrays alone; the result arrays fail closed; the call's shape (shape_ok, worked out by the caller from its arguments) is
+// refused; the fork takes its hold on the root's tables; the handle is looked up; an empty call ends.  body(set, vo) then runs with
+// c->mu and KtRead held, which is what KeySets::find asks of whoever uses the set.
+template <typename Set, typename Body>
+int verify_on_keyset(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, uint32_t max_ops, uint8_t* valid_out, uint8_t* status_out, bool dev, bool shape_ok,
+                     Body&& body) {
+  if (!c || n_ops > max_ops || (n_ops && (!valid_out || !status_out))) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  VerdictOut vo{valid_out, status_out, n_ops, dev};
+  if (const int rc = vo.fail_closed(c)) return rc;
+  if (!shape_ok) return BFTKV_E_INVALID;
+  KtRead kr(c);
+  if (kr.rc) return kr.rc;
+  const Set* ks = KeySets<Set>::find(c, keyset);
+  if (!ks) return KeySets<Set>::bad_handle(c);
+  if (n_ops == 0) return 0;
+  return body(*ks, vo);
+}
+
 int ecdsa_calculate_r_impl(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k, const int32_t* xs, const uint8_t* ri, const uint8_t* vi,
                            const uint8_t* curve, uint32_t bit_size, uint8_t* r_out, uint8_t* status_out, bool dev) {
   if (!c || !curve || bit_size == 0 || bit_size > 521 || k == 0 || k > 1024 || (uint64_t)n_ops * k > (1u << 24) ||
@@ -217,6 +238,48 @@ int ec_fb_table(bftkv_gpu_ctx* c, int id, const ecf::Curve<L>& C, const uint32_t
   return 0;
 }
 
+// The chain of an ECDSA verification, with the keys in the call or in a resident set: the per-signature arrays to the device, the
+// scratch, the result arrays, then k_ecv_prep, k_modinv (w = s^-1 mod N), k_ecv_base (u1 G from the curve's table `gtab` of width w)
+// and the kernel that adds u2 Q and compares.  Only that last one differs: key_kernel(C, grid, block, t) launches it on c->stream
+// over the scratch t.  mq: N's rows.
+struct EcvScratch { const uint32_t *r, *ki, *u2, *pt; const uint8_t *flag, *ibad; };
+template <int L, typename KeyKernel>
+int ecv_chain(bftkv_gpu_ctx* c, ScratchBufs& sb, VerdictOut& vo, const ecf::Curve<L>& C, uint32_t bit_size, const uint8_t* digests, uint32_t dlen,
+              const uint8_t* sigs, const uint32_t* key_idx, uint32_t n_keys, const ModTab& mq, const uint32_t* gtab, uint32_t w, uint32_t nwin,
+              KeyKernel&& key_kernel) {
+  const uint32_t n_ops = vo.n_ops, f = (bit_size + 7) / 8;
+  const bool dev = vo.dev;
+  uint32_t *d_gi, *d_ki = nullptr;
+  uint8_t *d_dg, *d_sig;
+  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt, *d_u2;
+  int rc;
+  if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
+  if (key_idx) {                                                                       // clamped on the device, for host callers too
+    uint32_t* raw;
+    if ((rc = to_dev(c, sb, key_idx, n_ops, &raw, dev)) || (rc = idx_to_dev(c, sb, raw, n_ops, n_keys, &d_ki, true))) return rc;
+  }
+  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
+  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * f, &d_sig, dev))) return rc;
+  if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
+      (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
+    return rc;
+  if ((rc = vo.device_arrays(c, sb))) return rc;
+  if ((rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_u2, false)) ||
+      (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_r, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * 3 * L * 4, &d_pt, false)))
+    return rc;
+  hipStream_t s = c->stream;
+  const dim3 grid((n_ops + EC_BLOCK - 1) / EC_BLOCK), block(EC_BLOCK);
+  hipLaunchKernelGGL(k_ecv_prep<L>, grid, block, 0, s, n_ops, (const uint8_t*)d_dg, dlen, bit_size, (const uint8_t*)d_sig, C, (uint32_t*)d_s28,
+                     (uint32_t*)d_e, (uint32_t*)d_r, (uint8_t*)d_flag);
+  // w = s^-1 mod N: the general inverse (N reaches 521 bits), as in CalculateR
+  hipLaunchKernelGGL(k_modinv, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint32_t*)d_s28, (const uint32_t*)d_gi, mq, (uint32_t*)d_w28,
+                     (uint8_t*)d_ibad, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+  hipLaunchKernelGGL(k_ecv_base<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint32_t*)d_e, (const uint32_t*)d_w28,
+                     (const uint8_t*)d_flag, C, gtab, w, nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
+  key_kernel(C, grid, block, EcvScratch{(const uint32_t*)d_r, d_ki, (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag, (const uint8_t*)d_ibad});
+  return vo.finish(c);
+}
+
 int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs, const uint32_t* key_idx,
                       uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, uint8_t* valid_out, uint8_t* status_out, bool dev) {
   if (!c || !curve || !keys || bit_size == 0 || bit_size > 521 || n_keys == 0 || n_keys > (1u << 24) || dlen == 0 || dlen > 66 || n_ops > (1u << 24) ||
@@ -234,45 +297,21 @@ int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, 
   ScratchBufs sb(c);
   { int grc = modtab_gc(c); if (grc) return grc; }
   ModTab mq;
-  uint32_t *d_gi, *d_ki = nullptr;
-  uint8_t *d_dg, *d_sig, *d_keys;
-  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2;
+  uint8_t* d_keys;
   if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq))) return rc;                      // N, for k_modinv
-  if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
-  if (key_idx) {                                                                       // clamped on the device, for host callers too
-    uint32_t* raw;
-    if ((rc = to_dev(c, sb, key_idx, n_ops, &raw, dev)) || (rc = idx_to_dev(c, sb, raw, n_ops, n_keys, &d_ki, true))) return rc;
-  }
-  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
-  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * f, &d_sig, dev))) return rc;
   if ((rc = to_dev(c, sb, keys, (size_t)n_keys * (1 + 2 * f), &d_keys))) return rc;
-  if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
-      (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
-    return rc;
-  if ((rc = vo.device_arrays(c, sb))) return rc;
-  hipStream_t s = c->stream;
   ec_dispatch(id, curve, [&](auto C) {
     constexpr int L = decltype(C)::kWords;
     const uint32_t* tab;
     uint32_t w, nwin;
     if ((rc = ec_fb_table<L>(c, id, C, &tab, &w, &nwin))) return;
-    if ((rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_u2, false)) ||
-        (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_r, false)) ||
-        (rc = dev_alloc(c, sb, (size_t)n_ops * 3 * L * 4, &d_pt, false)))
-      return;
-    const dim3 grid((n_ops + EC_BLOCK - 1) / EC_BLOCK), block(EC_BLOCK);
-    hipLaunchKernelGGL(k_ecv_prep<L>, grid, block, 0, s, n_ops, (const uint8_t*)d_dg, dlen, bit_size, (const uint8_t*)d_sig, C, (uint32_t*)d_s28,
-                       (uint32_t*)d_e, (uint32_t*)d_r, (uint8_t*)d_flag);
-    // w = s^-1 mod N: the general inverse (N reaches 521 bits), as in CalculateR
-    hipLaunchKernelGGL(k_modinv, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint32_t*)d_s28, (const uint32_t*)d_gi, mq, (uint32_t*)d_w28,
-                       (uint8_t*)d_ibad, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
-    hipLaunchKernelGGL(k_ecv_base<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint32_t*)d_e, (const uint32_t*)d_w28,
-                       (const uint8_t*)d_flag, C, tab, w, nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
-    hipLaunchKernelGGL(k_ecv_key<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint8_t*)d_keys, (const uint32_t*)d_ki, n_keys,
-                       (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag, (const uint8_t*)d_ibad, C, (uint8_t*)vo.d_valid, (uint8_t*)vo.d_st);
+    rc = ecv_chain<L>(c, sb, vo, C, bit_size, digests, dlen, sigs, key_idx, n_keys, mq, tab, w, nwin,
+                      [&](const ecf::Curve<L>& cv, dim3 grid, dim3 block, const EcvScratch& t) {
+                        hipLaunchKernelGGL(k_ecv_key<L>, grid, block, 0, c->stream, vo.n_ops, t.r, (const uint8_t*)d_keys, t.ki, n_keys, t.u2, t.pt, t.flag,
+                                           t.ibad, cv, (uint8_t*)vo.d_valid, (uint8_t*)vo.d_st);
+                      });
   });
-  if (rc) return rc;
-  return vo.finish(c);
+  return rc;
 }
 
 // ---- resident key sets ----------------------------------------------------------------------------------------------------
@@ -283,38 +322,21 @@ int ecdsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, 
 constexpr uint32_t EC_KEYSET_MAX_KEYS = 4096;
 constexpr size_t EC_KEYSET_TMP_BYTES = (size_t)256 << 20;      // k_ec_keytab_build's temporaries per launch: the keys go in chunks
 
-// caller holds c->mu and, on a fork, the root's key-table lock (KtRead)
-const EcKeySet* ec_keyset_find(const bftkv_gpu_ctx* c, int keyset) {
-  const bftkv_gpu_ctx* r = c->root ? c->root : c;
-  if (keyset < 0 || (size_t)keyset >= r->ec_keysets.size() || !r->ec_keysets[keyset].live) return nullptr;
-  return &r->ec_keysets[keyset];
-}
-
 int ecdsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys, const uint8_t* curve, uint32_t bit_size, int* keyset_out) {
   if (!c || !keys || !curve || !keyset_out || bit_size == 0 || bit_size > 521 || n_keys == 0 || n_keys > EC_KEYSET_MAX_KEYS) return BFTKV_E_INVALID;
   const int id = ec_curve_id(curve, bit_size);
   if (id < 0) return BFTKV_E_UNSUPPORTED;
   const uint32_t f = (bit_size + 7) / 8;
   ctx_lock lk(c->mu);
-  if (c->root) return fail(c, BFTKV_E_STATE, "ECDSA key sets are created on the root context; its forks see them");
-  HIPCHK(c, hipSetDevice(c->device));
-  ScratchBufs sb(c);
-  { int grc = modtab_gc(c); if (grc) return grc; }
-  EcKeySet ks;
   DevBuf tmp;
-  int rc = 0;
-  auto build = [&]() -> int {
+  const int created = KeySets<EcKeySet>::create(c, keyset_out, [&](EcKeySet& ks) -> int {
+    ScratchBufs sb(c);
+    { int grc = modtab_gc(c); if (grc) return grc; }
+    int rc = 0;
     ks.curve_id = id; ks.bits = bit_size; ks.n_keys = n_keys;
     ks.curve.assign(curve, curve + 5 * (size_t)f);
-    // N's Montgomery rows for k_modinv, copied out of the context's cache (which may drop them) into the set
-    ModTab mq;
-    if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq))) return rc;
-    const void* src[4] = {mq.n_limbs, mq.r2_limbs, mq.n0inv, mq.r2w_limbs};
-    const size_t len[4] = {MONT_N * 4, MONT_N * 4, 4, MONT_N_WIDE * 4};
-    for (int k = 0; k < 4; ++k) {
-      if (ks.mod[k].ensure(len[k]) != hipSuccess) { (void)hipGetLastError(); return fail(c, BFTKV_E_NOMEM, "ECDSA key set: device allocation failed"); }
-      HIPCHK(c, hipMemcpyAsync(ks.mod[k].p, src[k], len[k], hipMemcpyDeviceToDevice, c->stream));
-    }
+    ModTab mq;                                                                     // N's rows, for k_modinv
+    if ((rc = make_modtab(c, sb, curve + f, 1, f, &mq)) || (rc = ks.mod.copy_from<EcKeySet>(c, mq, 1, true))) return rc;
     uint8_t* d_keys;
     if ((rc = to_dev(c, sb, keys, (size_t)n_keys * (1 + 2 * f), &d_keys))) return rc;
     ec_dispatch(id, curve, [&](auto C) {
@@ -326,8 +348,7 @@ int ecdsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* k
       const size_t key_tmp = (size_t)ks.nwin * per * 2 * L * 4;
       const uint32_t chunk = (uint32_t)std::min<size_t>(n_keys, std::max<size_t>(1, EC_KEYSET_TMP_BYTES / key_tmp));
       if (ks.tab.ensure_exact(tab_bytes) != hipSuccess || ks.refused.ensure(n_keys) != hipSuccess || tmp.ensure_exact(chunk * key_tmp) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = fail(c, BFTKV_E_NOMEM, "ECDSA key set: device allocation failed");
+        rc = KeySets<EcKeySet>::nomem(c);
         return;
       }
       if (hipMemsetAsync(ks.tab.p, 0, tab_bytes, c->stream) != hipSuccess) { rc = fail(c, BFTKV_E_DEVICE, "hipMemsetAsync"); return; }
@@ -345,31 +366,15 @@ int ecdsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* k
     HIPCHK(c, hipGetLastError());
     for (uint8_t r : refused) ks.n_refused += r != 0;
     return 0;
-  };
-  rc = build();
-  tmp.release();
-  if (rc) { ks.release(); return rc; }
-  ks.live = true;
-  int h = -1;
-  for (size_t i = 0; i < c->ec_keysets.size(); ++i) if (!c->ec_keysets[i].live) { h = (int)i; break; }
-  KtWrite kw(c);
-  if (h < 0) { c->ec_keysets.emplace_back(); h = (int)c->ec_keysets.size() - 1; }
-  c->ec_keysets[h] = std::move(ks);
-  *keyset_out = h;
-  return 0;
+  });
+  tmp.release();          // (k_ec_keytab_build's temporaries: the stream is idle by now, built or not)
+  return created;
 }
 
 int ecdsa_keyset_destroy_impl(bftkv_gpu_ctx* c, int keyset) {
   if (!c) return BFTKV_E_INVALID;
   ctx_lock lk(c->mu);
-  if (c->root) return fail(c, BFTKV_E_STATE, "ECDSA key sets are destroyed on the root context");
-  if (!ec_keyset_find(c, keyset)) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle");
-  HIPCHK(c, hipSetDevice(c->device));
-  KtWrite kw(c);
-  HIPCHK(c, hipDeviceSynchronize());          // (_dev calls return before their kernels have run: nothing may still read the tables)
-  c->ec_keysets[keyset].release();
-  c->ec_keysets[keyset] = EcKeySet();
-  return 0;
+  return KeySets<EcKeySet>::retire(c, keyset);
 }
 
 int ecdsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* window_bits_out,
@@ -378,8 +383,8 @@ int ecdsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, u
   ctx_lock lk(c->mu);
   KtRead kr(c);
   if (kr.rc) return kr.rc;
-  const EcKeySet* ks = ec_keyset_find(c, keyset);
-  if (!ks) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle");
+  const EcKeySet* ks = KeySets<EcKeySet>::find(c, keyset);
+  if (!ks) return KeySets<EcKeySet>::bad_handle(c);
   if (n_keys_out) *n_keys_out = ks->n_keys;
   if (n_refused_out) *n_refused_out = ks->n_refused;
   if (window_bits_out) *window_bits_out = ks->w;
@@ -393,7 +398,7 @@ int ecdsa_keyset_table_impl(bftkv_gpu_ctx* c, int keyset, uint32_t key, uint32_t
   ctx_lock lk(c->mu);
   KtRead kr(c);
   if (kr.rc) return kr.rc;
-  const EcKeySet* ks = ec_keyset_find(c, keyset);
+  const EcKeySet* ks = KeySets<EcKeySet>::find(c, keyset);
   if (!ks || key >= ks->n_keys) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle or key index");
   if (cap_words < ks->key_words) return fail(c, BFTKV_E_NOMEM, "words_out holds less than one table");
   HIPCHK(c, hipSetDevice(c->device));
@@ -402,69 +407,32 @@ int ecdsa_keyset_table_impl(bftkv_gpu_ctx* c, int keyset, uint32_t key, uint32_t
   return 0;
 }
 
-// ecdsa_verify_impl over a registered set: the same k_ecv_prep, k_modinv and k_ecv_base, then k_ecv_key_tab.  Nothing is read
-// from host memory but the host form's own arrays (N's rows and both tables are resident), so the device form never waits.
+// ecdsa_verify_impl over a registered set: the same chain, ending in k_ecv_key_tab.  Nothing is read from host memory but the host
+// form's own arrays (N's rows and both tables are resident), so the device form never waits.
 int ecdsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t dlen, const uint8_t* sigs,
                              const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out, bool dev) {
-  if (!c || n_ops > (1u << 24) || (n_ops && (!valid_out || !status_out))) return BFTKV_E_INVALID;
-  ctx_lock lk(c->mu);
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  VerdictOut vo{valid_out, status_out, n_ops, dev};
-  if ((rc = vo.fail_closed(c))) return rc;
-  if (dlen == 0 || dlen > 66 || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
-  KtRead kr(c);
-  if (kr.rc) return kr.rc;
-  const EcKeySet* ks = ec_keyset_find(c, keyset);
-  if (!ks) return fail(c, BFTKV_E_INVALID, "bad ECDSA key set handle");
-  const uint32_t f = (ks->bits + 7) / 8;
-  if (n_ops == 0) return 0;
-  const bftkv_gpu_ctx* r = c->root ? c->root : c;
-  const int id = ks->curve_id;
-  // The root's G table is read here without the root's own lock (a fork holds KtRead, not r->mu).  That is safe because the root
-  // never rebuilds it: the window width is fixed when the context is made, ec_fb_table fills ec_fb_tab[id] / ec_fb_w[id] once per
-  // curve, and the set's creation did that before any fork could name the set.  So the check below cannot fail today; it is
-  // there for the day a context may change its width, which would have to take KtWrite.
-  if (r->ec_fb_w[id] != ks->w) return fail(c, BFTKV_E_STATE, "the G table of the key set's width is gone");
-  const uint32_t* gtab = r->ec_fb_tab[id].as<uint32_t>();
-  ScratchBufs sb(c);
-  ModTab mq;
-  mq.n_limbs = ks->mod[0].as<uint32_t>(); mq.r2_limbs = ks->mod[1].as<uint32_t>(); mq.n0inv = ks->mod[2].as<uint32_t>();
-  mq.r2w_limbs = ks->mod[3].as<uint32_t>();
-  uint32_t *d_gi, *d_ki = nullptr;
-  uint8_t *d_dg, *d_sig;
-  void *d_s28, *d_w28, *d_e, *d_r, *d_flag, *d_ibad, *d_pt = nullptr, *d_u2;
-  if ((rc = idx_to_dev(c, sb, nullptr, n_ops, 1, &d_gi, true))) return rc;
-  if (key_idx) {                                                                       // clamped on the device, for host callers too
-    uint32_t* raw;
-    if ((rc = to_dev(c, sb, key_idx, n_ops, &raw, dev)) || (rc = idx_to_dev(c, sb, raw, n_ops, ks->n_keys, &d_ki, true))) return rc;
-  }
-  if ((rc = to_dev(c, sb, digests, (size_t)n_ops * dlen, &d_dg, dev))) return rc;
-  if ((rc = to_dev(c, sb, sigs, (size_t)n_ops * 2 * f, &d_sig, dev))) return rc;
-  if ((rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_s28, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * MONT_N * 4, &d_w28, false)) ||
-      (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_flag, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_ibad, true)))
+  const bool shape_ok = dlen != 0 && dlen <= 66 && (!n_ops || (digests && sigs));
+  return verify_on_keyset<EcKeySet>(c, keyset, n_ops, 1u << 24, valid_out, status_out, dev, shape_ok, [&](const EcKeySet& ks, VerdictOut& vo) -> int {
+    const bftkv_gpu_ctx* r = c->root ? c->root : c;
+    const int id = ks.curve_id;
+    // The root's G table is read here without the root's own lock (a fork holds KtRead, not r->mu).  That is safe because the root
+    // never rebuilds it: the window width is fixed when the context is made, ec_fb_table fills ec_fb_tab[id] / ec_fb_w[id] once per
+    // curve, and the set's creation did that before any fork could name the set.  So the check below cannot fail today; it is
+    // there for the day a context may change its width, which would have to take KtWrite.
+    if (r->ec_fb_w[id] != ks.w) return fail(c, BFTKV_E_STATE, "the G table of the key set's width is gone");
+    const uint32_t* gtab = r->ec_fb_tab[id].as<uint32_t>();
+    ScratchBufs sb(c);
+    int rc = 0;
+    ec_dispatch(id, ks.curve.data(), [&](auto C) {
+      constexpr int L = decltype(C)::kWords;
+      rc = ecv_chain<L>(c, sb, vo, C, ks.bits, digests, dlen, sigs, key_idx, ks.n_keys, ks.mod.view(), gtab, ks.w, ks.nwin,
+                        [&](const ecf::Curve<L>& cv, dim3 grid, dim3 block, const EcvScratch& t) {
+                          hipLaunchKernelGGL(k_ecv_key_tab<L>, grid, block, 0, c->stream, vo.n_ops, t.r, ks.tab.as<uint32_t>(), ks.refused.as<uint8_t>(), t.ki,
+                                             ks.n_keys, ks.w, ks.nwin, t.u2, t.pt, t.flag, t.ibad, cv, (uint8_t*)vo.d_valid, (uint8_t*)vo.d_st);
+                        });
+    });
     return rc;
-  if ((rc = vo.device_arrays(c, sb))) return rc;
-  hipStream_t s = c->stream;
-  ec_dispatch(id, ks->curve.data(), [&](auto C) {
-    constexpr int L = decltype(C)::kWords;
-    if ((rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_e, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_u2, false)) ||
-        (rc = dev_alloc(c, sb, (size_t)n_ops * L * 4, &d_r, false)) ||
-        (rc = dev_alloc(c, sb, (size_t)n_ops * 3 * L * 4, &d_pt, false)))
-      return;
-    const dim3 grid((n_ops + EC_BLOCK - 1) / EC_BLOCK), block(EC_BLOCK);
-    hipLaunchKernelGGL(k_ecv_prep<L>, grid, block, 0, s, n_ops, (const uint8_t*)d_dg, dlen, ks->bits, (const uint8_t*)d_sig, C, (uint32_t*)d_s28,
-                       (uint32_t*)d_e, (uint32_t*)d_r, (uint8_t*)d_flag);
-    hipLaunchKernelGGL(k_modinv, dim3((n_ops + 63) / 64), dim3(64), 0, s, n_ops, (const uint32_t*)d_s28, (const uint32_t*)d_gi, mq, (uint32_t*)d_w28,
-                       (uint8_t*)d_ibad, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
-    hipLaunchKernelGGL(k_ecv_base<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, (const uint32_t*)d_e, (const uint32_t*)d_w28,
-                       (const uint8_t*)d_flag, C, gtab, ks->w, ks->nwin, (uint32_t*)d_pt, (uint32_t*)d_u2);
-    hipLaunchKernelGGL(k_ecv_key_tab<L>, grid, block, 0, s, n_ops, (const uint32_t*)d_r, ks->tab.as<uint32_t>(), ks->refused.as<uint8_t>(),
-                       (const uint32_t*)d_ki, ks->n_keys, ks->w, ks->nwin, (const uint32_t*)d_u2, (const uint32_t*)d_pt, (const uint8_t*)d_flag,
-                       (const uint8_t*)d_ibad, C, (uint8_t*)vo.d_valid, (uint8_t*)vo.d_st);
   });
-  if (rc) return rc;
-  return vo.finish(c);
 }
 
 }  // namespace

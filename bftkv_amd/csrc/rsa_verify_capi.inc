@@ -53,11 +53,6 @@ void rsav_rows(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys_n, const u
   }
 }
 
-// lanes per signature as for k_multiexp: 8 while the signatures leave at most one wave per SIMD, else 4 (BFTKV_RSAV_LANES overrides)
-inline bool rsav_wide(const bftkv_gpu_ctx* c, uint32_t n_ops) {
-  return c->rsav_lanes ? c->rsav_lanes == 8 : (uint64_t)n_ops * MULTI_TPI8 <= (uint64_t)c->n_cus * 4 * 64;
-}
-
 // what refuses a call whatever its keys: BFTKV_E_INVALID
 inline bool rsav_shape_ok(uint32_t hash_id, uint32_t dlen, uint32_t nbytes) {
   return rsav_prefix_len(hash_id) >= 0 && rsav_dlen_ok(hash_id, dlen) && nbytes != 0 && nbytes <= RSAV_MAX_NBYTES;
@@ -101,7 +96,7 @@ int rsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, ui
     return BFTKV_E_INVALID;
   if (n_ops == 0) return 0;
   ScratchBufs sb(c);
-  const bool wide = rsav_wide(c, n_ops);
+  const bool wide = lanes_wide(c, c->rsav_lanes, n_ops);      // lanes per signature as for k_multiexp (BFTKV_RSAV_LANES overrides)
   RsavRows rows;
   rsav_rows(c, n_keys, keys_n, keys_e, nbytes, wide, &rows);
   uint32_t *d_n, *d_r2, *d_meta;
@@ -113,21 +108,11 @@ int rsa_verify_impl(bftkv_gpu_ctx* c, uint32_t n_ops, const uint8_t* digests, ui
 }
 
 // ---- resident key sets: created and destroyed on the root under KtWrite, read by the forks under KtRead (as DSA key sets are) ----
-// caller holds c->mu and, on a fork, the root's key-table lock (KtRead)
-const RsaKeySet* rsa_keyset_find(const bftkv_gpu_ctx* c, int keyset) {
-  const bftkv_gpu_ctx* r = c->root ? c->root : c;
-  if (keyset < 0 || (size_t)keyset >= r->rsa_keysets.size() || !r->rsa_keysets[keyset].live) return nullptr;
-  return &r->rsa_keysets[keyset];
-}
-
 int rsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* keys_n, const uint32_t* keys_e, uint32_t nbytes, int* keyset_out) {
   if (!c || !keys_n || !keys_e || !keyset_out || n_keys == 0 || n_keys > RSA_KEYSET_MAX_KEYS || nbytes == 0 || nbytes > RSAV_MAX_NBYTES)
     return BFTKV_E_INVALID;
   ctx_lock lk(c->mu);
-  if (c->root) return fail(c, BFTKV_E_STATE, "RSA key sets are created on the root context; its forks see them");
-  HIPCHK(c, hipSetDevice(c->device));
-  RsaKeySet ks;
-  auto build = [&]() -> int {
+  return KeySets<RsaKeySet>::create(c, keyset_out, [&](RsaKeySet& ks) -> int {
     ks.n_keys = n_keys; ks.nbytes = nbytes;
     for (int wide = 0; wide < 2; ++wide) {
       RsavRows rows;
@@ -136,40 +121,21 @@ int rsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* key
       DevBuf& dn = wide ? ks.n80 : ks.n29;
       DevBuf& dr = wide ? ks.r2_80 : ks.r2_29;
       if (dn.ensure_exact(rows.n.size() * 4) != hipSuccess || dr.ensure_exact(rows.r2.size() * 4) != hipSuccess ||
-          ks.meta.ensure_exact(rows.meta.size() * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, BFTKV_E_NOMEM, "RSA key set: device allocation failed");
-      }
+          ks.meta.ensure_exact(rows.meta.size() * 4) != hipSuccess)
+        return KeySets<RsaKeySet>::nomem(c);
       HIPCHK(c, hipMemcpyAsync(dn.p, rows.n.data(), rows.n.size() * 4, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipMemcpyAsync(dr.p, rows.r2.data(), rows.r2.size() * 4, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipMemcpyAsync(ks.meta.p, rows.meta.data(), rows.meta.size() * 4, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));          // (the host vectors die with this round)
     }
     return 0;
-  };
-  const int rc = build();
-  if (rc) { (void)hipStreamSynchronize(c->stream); ks.release(); return rc; }
-  ks.live = true;
-  int h = -1;
-  for (size_t i = 0; i < c->rsa_keysets.size(); ++i) if (!c->rsa_keysets[i].live) { h = (int)i; break; }
-  KtWrite kw(c);
-  if (h < 0) { c->rsa_keysets.emplace_back(); h = (int)c->rsa_keysets.size() - 1; }
-  c->rsa_keysets[h] = std::move(ks);
-  *keyset_out = h;
-  return 0;
+  });
 }
 
 int rsa_keyset_destroy_impl(bftkv_gpu_ctx* c, int keyset) {
   if (!c) return BFTKV_E_INVALID;
   ctx_lock lk(c->mu);
-  if (c->root) return fail(c, BFTKV_E_STATE, "RSA key sets are destroyed on the root context");
-  if (!rsa_keyset_find(c, keyset)) return fail(c, BFTKV_E_INVALID, "bad RSA key set handle");
-  HIPCHK(c, hipSetDevice(c->device));
-  KtWrite kw(c);
-  HIPCHK(c, hipDeviceSynchronize());          // (_dev calls return before their kernels have run: nothing may still read the rows)
-  c->rsa_keysets[keyset].release();
-  c->rsa_keysets[keyset] = RsaKeySet();
-  return 0;
+  return KeySets<RsaKeySet>::retire(c, keyset);
 }
 
 int rsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* nbytes_out) {
@@ -177,8 +143,8 @@ int rsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uin
   ctx_lock lk(c->mu);
   KtRead kr(c);
   if (kr.rc) return kr.rc;
-  const RsaKeySet* ks = rsa_keyset_find(c, keyset);
-  if (!ks) return fail(c, BFTKV_E_INVALID, "bad RSA key set handle");
+  const RsaKeySet* ks = KeySets<RsaKeySet>::find(c, keyset);
+  if (!ks) return KeySets<RsaKeySet>::bad_handle(c);
   if (n_keys_out) *n_keys_out = ks->n_keys;
   if (n_refused_out) *n_refused_out = ks->n_refused;
   if (nbytes_out) *nbytes_out = ks->nbytes;
@@ -188,22 +154,13 @@ int rsa_keyset_info_impl(bftkv_gpu_ctx* c, int keyset, uint32_t* n_keys_out, uin
 // rsa_verify_impl over a registered set: nothing crosses but digests, signatures and indices, so the device form never waits
 int rsa_verify_keyset_impl(bftkv_gpu_ctx* c, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen, const uint8_t* sigs,
                            const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out, bool dev) {
-  if (!c || n_ops > RSAV_MAX_OPS || (n_ops && (!valid_out || !status_out))) return BFTKV_E_INVALID;
-  ctx_lock lk(c->mu);
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  VerdictOut vo{valid_out, status_out, n_ops, dev};
-  if ((rc = vo.fail_closed(c))) return rc;
-  if (!rsav_shape_ok(hash_id, dlen, 1) || (n_ops && (!digests || !sigs))) return BFTKV_E_INVALID;
-  KtRead kr(c);
-  if (kr.rc) return kr.rc;
-  const RsaKeySet* ks = rsa_keyset_find(c, keyset);
-  if (!ks) return fail(c, BFTKV_E_INVALID, "bad RSA key set handle");
-  if (n_ops == 0) return 0;
-  ScratchBufs sb(c);
-  const bool wide = rsav_wide(c, n_ops);
-  const RsavKeys keys{(wide ? ks->n80 : ks->n29).as<uint32_t>(), (wide ? ks->r2_80 : ks->r2_29).as<uint32_t>(), ks->meta.as<uint4>()};
-  return rsav_launch(c, sb, vo, digests, hash_id, dlen, sigs, ks->nbytes, key_idx, ks->n_keys, keys, wide);
+  const bool shape_ok = rsav_shape_ok(hash_id, dlen, 1) && (!n_ops || (digests && sigs));
+  return verify_on_keyset<RsaKeySet>(c, keyset, n_ops, RSAV_MAX_OPS, valid_out, status_out, dev, shape_ok, [&](const RsaKeySet& ks, VerdictOut& vo) -> int {
+    ScratchBufs sb(c);
+    const bool wide = lanes_wide(c, c->rsav_lanes, n_ops);
+    const RsavKeys keys{(wide ? ks.n80 : ks.n29).as<uint32_t>(), (wide ? ks.r2_80 : ks.r2_29).as<uint32_t>(), ks.meta.as<uint4>()};
+    return rsav_launch(c, sb, vo, digests, hash_id, dlen, sigs, ks.nbytes, key_idx, ks.n_keys, keys, wide);
+  });
 }
 
 }  // namespace

@@ -117,6 +117,13 @@ int idx_to_dev(bftkv_gpu_ctx* c, ScratchBufs& sb, const uint32_t* idx, uint32_t 
   *out = b->as<uint32_t>();
   return 0;
 }
+// lanes per number: 8 while that still leaves at most one wave per SIMD (8192 operations on 256 CUs), else 4.  The call is
+// as long as its longest-loaded SIMD: an 8-lane wave runs 0.68x the instructions of a 4-lane one (measured: the m-broadcast
+// and window shifts do not shrink with the limbs), so 8 lanes win only while no SIMD gets two of them -- 10,000 operations:
+// 4 lanes 10.3 ms, 8 lanes 12.8 ms (1250 waves on 1024 SIMDs).  knob: the caller's experiment knob (4 | 8 overrides, 0 = by size).
+inline bool lanes_wide(const bftkv_gpu_ctx* c, uint32_t knob, uint64_t n_ops) {
+  return knob ? knob == 8 : n_ops * MULTI_TPI8 <= (uint64_t)c->n_cus * 4 * 64;
+}
 // end of a call: host callers wait for their results; device callers stay asynchronous on the context's stream
 int finish(bftkv_gpu_ctx* c, bool dev) {
   if (!dev) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -307,19 +314,13 @@ int dsa_calculate_r_impl(bftkv_gpu_ctx* c, uint32_t n_ops, uint32_t k, const int
     // SMALL calls (a lone DistSign, a micro-batch of a few dozen): the call lasts as long as one wave's chain of dependent products
     // whatever the instruction count, so the bases are spread over as many quad groups as still get a SIMD each -- k = 8 bases on 8
     // groups: 15 + 256 + 64 products per group, 8 to multiply the partial products up, instead of 120 + 256 + 512 in one chain.
-    const uint64_t cap = (uint64_t)c->n_cus * 4 * 64;       // lanes of one wave per SIMD
     for (uint32_t pp = k; pp > parts; --pp)
-      if (k % pp == 0 && (uint64_t)n_ops * pp * MULTI_TPI8 <= cap) { parts = pp; break; }
+      if (k % pp == 0 && lanes_wide(c, 0, (uint64_t)n_ops * pp)) { parts = pp; break; }      // (eight lanes each, one wave per SIMD)
   }
   // exponents are residues mod q: qbytes * 2 four-bit windows
   const uint32_t ew = qbytes * 2;
-  // lanes per number: 8 while that still leaves at most one wave per SIMD (8192 operations on 256 CUs), else 4.  The call is
-  // as long as its longest-loaded SIMD: an 8-lane wave runs 0.68x the instructions of a 4-lane one (measured: the m-broadcast
-  // and window shifts do not shrink with the limbs), so 8 lanes win only while no SIMD gets two of them -- 10,000 operations:
-  // 4 lanes 10.3 ms, 8 lanes 12.8 ms (1250 waves on 1024 SIMDs).
   auto multiexp = [&](uint32_t ops, uint32_t kb, const uint32_t* bases, const uint32_t* exps, uint32_t* out, uint32_t div) {
-    const bool wide = c->multiexp_lanes ? c->multiexp_lanes == 8 : (uint64_t)ops * MULTI_TPI8 <= (uint64_t)c->n_cus * 4 * 64;
-    if (wide)
+    if (lanes_wide(c, c->multiexp_lanes, ops))
       hipLaunchKernelGGL((k_multiexp<MULTI_L8, MULTI_TPI8>), dim3((ops + RSA_BLOCK / MULTI_TPI8 - 1) / (RSA_BLOCK / MULTI_TPI8)), dim3(RSA_BLOCK), 0, s,
                          ops, kb, bases, exps, d_gi, mp, (uint32_t*)d_scr, out, div, ew);
     else if (c->multiexp_block == 64)

@@ -94,6 +94,46 @@ def test_handles_forks_and_the_device_form(gpu_ctx):
     gpu_ctx.rsa_keyset_destroy(b)
 
 
+def test_handle_spaces_of_the_three_kinds_are_independent(gpu_ctx):
+    """One set of each kind, each the smallest its own tests use.  Retiring the ECDSA set leaves the DSA and the RSA set answering,
+    also where their handles have the retired one's number, and the next ECDSA set takes that number again."""
+    import json
+    import os
+    import dsa_verify_cases as DK
+    import dsa_verify_ref as DV
+    import ec_ref as E
+    lib, curve = gpu_ctx.lib, E.CURVES["P-256"]
+    pts, pst = gpu_ctx.ec_scalar_base_mult([0x1234567], curve)
+    assert not pst.any()
+    k = json.load(open(os.path.join(DK.GOLDEN, "keys_dsa1024.json")))["keys"][0]
+    p, q, g, x = (int(k[f], 16) for f in ("p", "q", "g", "x"))
+    assert p.bit_length() == 1024 and q.bit_length() == 160
+    rng = np.random.default_rng(8)
+    ddg, rs = rng.bytes(20), None
+    while rs is None:
+        rs = DK.sign(p, q, g, x, ddg, DK.rnd(rng, q) or 1)
+    assert DV.verify(p, q, g, pow(g, x, p), ddg, *rs) == (1, DV.OK)
+    rcase = next(c for c in K.cell("rsa2048", 8, 32) if c.part == "honest" and want([c]) == [(1, V.OK)])
+    e = gpu_ctx.ecdsa_keyset_create([pts[0]], curve)
+    d = gpu_ctx.dsa_keyset_create([(0, pow(g, x, p))], [(p, q, g)], window_bits=4)
+    r = gpu_ctx.rsa_keyset_create([(rcase.n, rcase.e)], nbytes=256)
+    try:
+        gpu_ctx.ecdsa_keyset_destroy(e)
+        assert lib.bftkv_gpu_ecdsa_keyset_info(gpu_ctx.h, e, None, None, None, None) == E_INVALID
+        assert gpu_ctx.dsa_keyset_info(d)["n_keys"] == 1 and gpu_ctx.dsa_keyset_info(d)["window_bits"] == 4
+        assert gpu_ctx.rsa_keyset_info(r) == dict(n_keys=1, n_refused=0, nbytes=256)
+        valid, st = gpu_ctx.dsa_verify_keyset(d, [ddg], [rs[0].to_bytes(20, "big") + rs[1].to_bytes(20, "big")])
+        assert (int(valid[0]), int(st[0])) == (1, 0)
+        valid, st = gpu_ctx.rsa_verify_keyset(r, [rcase.digest], [rcase.s.to_bytes(256, "big")], 8)
+        assert (int(valid[0]), int(st[0])) == (1, 0)
+        e2 = gpu_ctx.ecdsa_keyset_create([pts[0]], curve)
+        assert e2 == e and gpu_ctx.ecdsa_keyset_info(e2)["n_keys"] == 1
+        gpu_ctx.ecdsa_keyset_destroy(e2)
+    finally:
+        gpu_ctx.dsa_keyset_destroy(d)
+        gpu_ctx.rsa_keyset_destroy(r)
+
+
 def test_batcher_through_a_key_set(gpu_ctx):
     """64 threads, one signature per call under the keys of one set: three modulus sizes, two hashes and hash id 0, valid, invalid and
     fenced mixed; one caller with a wrong dlen and one with a dead handle are refused alone."""

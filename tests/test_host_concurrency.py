@@ -1,6 +1,6 @@
 """The host side of the library entered by many threads at once, without a GPU: tools/tsan_host.sh builds csrc/capi.hip for the host
 with ThreadSanitizer over tools/fakehip (a stand-in HIP runtime whose kernels do not run) and drives every micro-batcher entry,
-pipelined host-buffer calls on forked contexts and a keyring / quorum writer concurrently (tools/fakehip/stress.c) -- the shape of
+pipelined host-buffer calls on forked contexts, readers of a resident RSA key set and a keyring / quorum / key-set writer concurrently (tools/fakehip/stress.c) -- the shape of
 protocol.Server's goroutine per request (transport/http/http.go:85,143 -> protocol/server.go:562-620).  Checked: every call returns,
 a call that fails leaves a failing status byte, ThreadSanitizer prints nothing.  Answers are not checked here (no kernels): the
 -m gpu tests do that through the same entries."""
@@ -30,7 +30,7 @@ def test_every_batcher_entry_under_thread_sanitizer(tmp_path):
     # from the register, a keyring change forgets it, the two requests after it repeat that
     assert got["register"] == [0, 1, 0, 1], got["register"]
     kinds = ("collective", "signature", "certificate", "modmul_product", "lagrange_combine", "dsa_calculate_r", "modexp", "host_buffer_call",
-             "keyring_set", "quorum_create_destroy")
+             "keyring_set", "quorum_create_destroy", "rsa_keyset_create_destroy", "rsa_verify_keyset")
     for kind in kinds:
         assert got[kind]["rc_nonzero"] == 0, (kind, got[kind])
     # how far each kind gets in a few seconds under the sanitizer depends on the machine: every kind normally runs, the mix must

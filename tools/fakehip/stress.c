@@ -1,7 +1,7 @@
 /* Every kind of caller of libbftkv_gpu.so's host side at once, for ThreadSanitizer (tools/tsan_host.sh) over tools/fakehip:
  * one-operation callers of every micro-batcher entry (collective / signature / certificate / message verification, the four
- * threshold combines), big host-buffer calls through the pipelined path on forked contexts, and a writer that replaces the key
- * table and creates / destroys quorums meanwhile -- the mix protocol.Server's goroutines make (server.go:562-620) while
+ * threshold combines), big host-buffer calls through the pipelined path on forked contexts, readers of a resident RSA key set (which
+ * needs no kernel to be made), and a writer that replaces the key table and creates / destroys quorums and key sets meanwhile -- the mix protocol.Server's goroutines make (server.go:562-620) while
  * Protocol.Joining / Leaving change the keyring (protocol.go:21-60).  Kernels do not run there: answers are not checked, only
  * that every call returns, fails closed when it fails, and that TSan stays silent.
  *   stress corpus.bin extras.bin [seconds = 5] [callers per kind = 8] [lanes = 3] [writer pause ms = 200; 0 = no writer]
@@ -30,6 +30,10 @@ static bftkv_gpu_pubkey* g_keys;
 static uint32_t g_nkeys;
 static bftkv_gpu_qc g_qc;
 static long g_writer_ms = 200;
+static uint8_t g_rsa_n[2 * 256];          /* two 2048-bit moduli of the corpus: the keys of both RSA key sets */
+static const uint32_t g_rsa_e[2] = {65537, 65537};
+static int g_rsa_set = -1;                /* long-lived, made before the threads start */
+static atomic_int g_rsa_transient = -1;   /* the handle the writer's set has while it lives (the writer makes and retires it) */
 
 static uint32_t rnd(uint32_t* s) { *s = *s * 1664525u + 1013904223u; return *s >> 8; }
 static void fill(uint8_t* p, size_t n, uint32_t* s) { for (size_t i = 0; i < n; ++i) p[i] = (uint8_t)rnd(s); }
@@ -142,18 +146,55 @@ static void* host_buffers(void* a) {
   return NULL;
 }
 
-/* the writer: Joining / Leaving replace the keyring, quorums come and go */
+/* Readers of the key-set registry: the long-lived set through a fork's own call and through the batcher, which must both succeed.
+ * One reader in four also names the writer's transient handle, by either way: there is such a set or there is not (0 or
+ * BFTKV_E_INVALID, never anything else), and a refusal leaves failed statuses and zero verdicts.  Both sets have 256-byte keys. */
+static void* rsa_keyset(void* a) {
+  uint32_t s = (uint32_t)(size_t)a * 49979687u + 13;
+  const int probes = ((size_t)a & 3) == 0;
+  static const uint32_t idx[4] = {0, 1, 1, 0};
+  bftkv_gpu_ctx* fork = NULL;
+  if (bftkv_gpu_ctx_fork(g_ctx, &fork)) { note(12, 1); return NULL; }
+  uint8_t *dg = malloc(4 * 32), *sig = malloc(4 * 256), valid[4], st[4];
+  while (!atomic_load(&g_stop)) {
+    fill(dg, 4 * 32, &s); fill(sig, 4 * 256, &s);
+    note(12, bftkv_gpu_rsa_verify_keyset(fork, g_rsa_set, 4, dg, 0, 32, sig, idx, valid, st));
+    note(12, bftkv_gpu_batcher_rsa_verify_keyset(g_b, g_rsa_set, rnd(&s) & 1, dg, 0, 32, sig, valid, st));
+    if (!probes) continue;
+    const int h = atomic_load(&g_rsa_transient), n = (rnd(&s) & 1) ? 4 : 1;
+    memset(valid, 0xEE, 4); memset(st, 0, 4);
+    const int rc = n == 4 ? bftkv_gpu_rsa_verify_keyset(fork, h, 4, dg, 0, 32, sig, idx, valid, st)
+                          : bftkv_gpu_batcher_rsa_verify_keyset(g_b, h, 1, dg, 0, 32, sig, valid, st);
+    int closed = rc == 0 || rc == BFTKV_E_INVALID;
+    for (int i = 0; rc && i < n; ++i) closed = closed && st[i] == BFTKV_TH_FAILED && valid[i] == 0;
+    if (!closed) atomic_fetch_add(&g_not_closed, 1);
+  }
+  free(dg); free(sig);
+  bftkv_gpu_destroy(fork);
+  return NULL;
+}
+
+/* the writer: Joining / Leaving replace the keyring, quorums and key sets come and go */
 static void* writer(void* a) {
   (void)a;
   struct timespec nap = {g_writer_ms / 1000, (g_writer_ms % 1000) * 1000000};
   while (!atomic_load(&g_stop)) {
     nanosleep(&nap, NULL);
     if (atomic_load(&g_stop)) break;
-    note(9, bftkv_gpu_keyring_set(g_ctx, g_keys, g_nkeys));
-    int q = -1;
-    int rc = bftkv_gpu_quorum_create(g_ctx, &g_qc, 1, &q);
-    if (!rc) rc = bftkv_gpu_quorum_destroy(g_ctx, q);
-    note(10, rc);
+    /* a transient key set eight times over; the first lives through the keyring and quorum work */
+    for (int round = 0; round < 8 && !atomic_load(&g_stop); ++round) {
+      int ks = -1;
+      const int ks_rc = bftkv_gpu_rsa_keyset_create(g_ctx, 2, g_rsa_n, g_rsa_e, 256, &ks);
+      if (!ks_rc) atomic_store(&g_rsa_transient, ks);
+      if (round == 0) {
+        note(9, bftkv_gpu_keyring_set(g_ctx, g_keys, g_nkeys));
+        int q = -1;
+        int rc = bftkv_gpu_quorum_create(g_ctx, &g_qc, 1, &q);
+        if (!rc) rc = bftkv_gpu_quorum_destroy(g_ctx, q);
+        note(10, rc);
+      }
+      note(11, ks_rc ? ks_rc : bftkv_gpu_rsa_keyset_destroy(g_ctx, ks));
+    }
     uint64_t st[4], ns[8];
     bftkv_gpu_batcher_stats(g_b, st);
     bftkv_gpu_batcher_times(g_b, ns);
@@ -205,6 +246,9 @@ int main(int argc, char** argv) {
   if (bftkv_gpu_keyring_set(g_ctx, g_keys, g_nkeys)) { fprintf(stderr, "keyring: %s\n", bftkv_gpu_last_error(g_ctx)); return 1; }
   g_qc.f = qn[0]; g_qc.min = qn[1]; g_qc.threshold = qn[2]; g_qc.suff = qn[3]; g_qc.node_ids = ids; g_qc.n_nodes = g_nkeys;
   if (bftkv_gpu_quorum_create(g_ctx, &g_qc, 1, &g_quorum)) { fprintf(stderr, "quorum: %s\n", bftkv_gpu_last_error(g_ctx)); return 1; }
+  if (g_nkeys < 2) { fprintf(stderr, "corpus: fewer than two keys\n"); return 2; }
+  memcpy(g_rsa_n, g_keys[0].n, 256); memcpy(g_rsa_n + 256, g_keys[1].n, 256);
+  if (bftkv_gpu_rsa_keyset_create(g_ctx, 2, g_rsa_n, g_rsa_e, 256, &g_rsa_set)) { fprintf(stderr, "RSA key set: %s\n", bftkv_gpu_last_error(g_ctx)); return 1; }
   g_b = bftkv_gpu_batcher_create_lanes(g_ctx, 64, 0, lanes);
   if (!g_b) { fprintf(stderr, "batcher: %s\n", bftkv_gpu_last_error(g_ctx)); return 1; }
 
@@ -226,13 +270,13 @@ int main(int argc, char** argv) {
       reg[step] = (int)(ns[7] - before);
     }
   }
-  void* (*kinds[5])(void*) = {collective, signature, certificate, message, threshold};
-  const int n_threads = 5 * per_kind + 3;
+  void* (*kinds[6])(void*) = {collective, signature, certificate, message, threshold, rsa_keyset};
+  const int n_threads = 6 * per_kind + 3;
   pthread_t* th = malloc(sizeof(pthread_t) * (size_t)n_threads);
   int t = 0;
   /* (certificate calls run on the root context under its lock, and with kernels that do not run their ReadEntity verdicts are
    * never remembered: a quarter of the callers, so that the lanes see traffic too) */
-  for (int k = 0; k < 5; ++k) for (int j = 0; j < (k == 2 ? (per_kind + 3) / 4 : per_kind); ++j, ++t) pthread_create(&th[t], NULL, kinds[k], (void*)(size_t)(t + 1));
+  for (int k = 0; k < 6; ++k) for (int j = 0; j < (k == 2 ? (per_kind + 3) / 4 : per_kind); ++j, ++t) pthread_create(&th[t], NULL, kinds[k], (void*)(size_t)(t + 1));
   pthread_create(&th[t++], NULL, host_buffers, NULL);
   pthread_create(&th[t++], NULL, host_buffers, NULL);
   if (g_writer_ms > 0) pthread_create(&th[t++], NULL, writer, NULL);
@@ -242,10 +286,10 @@ int main(int argc, char** argv) {
   for (int i = 0; i < t; ++i) pthread_join(th[i], NULL);
   bftkv_gpu_batcher_destroy(g_b);
   bftkv_gpu_destroy(g_ctx);
-  static const char* name[11] = {"collective", "signature", "certificate", "message", "modmul_product", "lagrange_combine", "dsa_calculate_r", "modexp",
-                                 "host_buffer_call", "keyring_set", "quorum_create_destroy"};
+  static const char* name[13] = {"collective", "signature", "certificate", "message", "modmul_product", "lagrange_combine", "dsa_calculate_r", "modexp",
+                                 "host_buffer_call", "keyring_set", "quorum_create_destroy", "rsa_keyset_create_destroy", "rsa_verify_keyset"};
   printf("{");
-  for (int k = 0; k < 11; ++k) printf("\"%s\": {\"calls\": %llu, \"rc_nonzero\": %llu, \"first_rc\": %d}, ", name[k], atomic_load(&g_calls[k]), atomic_load(&g_failed[k]), atomic_load(&g_first_rc[k]));
+  for (int k = 0; k < 13; ++k) printf("\"%s\": {\"calls\": %llu, \"rc_nonzero\": %llu, \"first_rc\": %d}, ", name[k], atomic_load(&g_calls[k]), atomic_load(&g_failed[k]), atomic_load(&g_first_rc[k]));
   printf("\"register\": [%d, %d, %d, %d], \"failed_open\": %llu}\n", reg[0], reg[1], reg[2], reg[3], atomic_load(&g_not_closed));
   return atomic_load(&g_not_closed) ? 1 : 0;
 }

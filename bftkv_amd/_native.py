@@ -56,6 +56,7 @@ EXPORTS = [
     "bftkv_gpu_dsa_verify_keyset_dev", "bftkv_gpu_batcher_dsa_verify_keyset", "bftkv_gpu_selftest_dsa_keyset_table",
     "bftkv_gpu_rsa_verify", "bftkv_gpu_rsa_verify_dev", "bftkv_gpu_rsa_keyset_create", "bftkv_gpu_rsa_keyset_destroy", "bftkv_gpu_rsa_keyset_info",
     "bftkv_gpu_rsa_verify_keyset", "bftkv_gpu_rsa_verify_keyset_dev", "bftkv_gpu_batcher_rsa_verify", "bftkv_gpu_batcher_rsa_verify_keyset",
+    "bftkv_gpu_tpa_yi", "bftkv_gpu_tpa_bi", "bftkv_gpu_tpa_ni", "bftkv_gpu_batcher_tpa_yi", "bftkv_gpu_batcher_tpa_bi",
 ]
 
 _lib = None
@@ -175,6 +176,11 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_rsa_verify_keyset_dev.argtypes = lib.bftkv_gpu_rsa_verify_keyset.argtypes
     lib.bftkv_gpu_batcher_rsa_verify.argtypes = [vp, u8p, u32, u32, u8p, u32, u8p, u32, u8p, u8p]
     lib.bftkv_gpu_batcher_rsa_verify_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u32, u8p, u8p, u8p]
+    lib.bftkv_gpu_tpa_yi.argtypes = [vp, u32, u8p, u32, u8p, u32, vp, u32, u8p, u8p, u8p]
+    lib.bftkv_gpu_tpa_bi.argtypes = [vp, u32, u8p, u8p, vp, u32, u8p, u32, u8p, u32, vp, u32, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_tpa_ni.argtypes = [vp, u32, u8p, u8p, vp, u32, u8p, u32, u8p, u32, vp, u32, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_batcher_tpa_yi.argtypes = [vp, u8p, u32, u8p, u32, u8p, u8p, u8p]
+    lib.bftkv_gpu_batcher_tpa_bi.argtypes = [vp, u8p, u8p, u32, u32, u8p, u32, u8p, u32, u8p, u8p, u8p, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -787,6 +793,48 @@ class Context:
         return self._verdicts("rsa_verify_keyset", "digests of one length, sigs of the set's nbytes", digests, sigs, self.rsa_keyset_info(keyset)["nbytes"], key_idx,
                               lambda n, dg, dlen, sg, ki, valid, st: self.lib.bftkv_gpu_rsa_verify_keyset(self.h, keyset, n, dg, hash_id, dlen, sg, ki, valid, st))
 
+    # ---- threshold password authentication (crypto/auth): rows of uint8, big-endian
+    def tpa_yi(self, x, y, mods, mod_idx=None):
+        """makeYi: yi[i] = x[i] ^ y[i] mod mods[mod_idx[i]].  x [n, nbytes], y [n, exp_len], mods [m, nbytes], mod_idx [n] or None
+        (modulus 0) -> (yi [n, nbytes], status [n])."""
+        x, y, mods = _u8(x), _u8(y), _u8(mods)
+        mi = None if mod_idx is None else np.ascontiguousarray(mod_idx, dtype=np.uint32)
+        assert y.shape[0] == x.shape[0]
+        out, st = np.zeros_like(x), np.zeros(x.shape[0], dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_tpa_yi(self.h, x.shape[0], _ptr(x), x.shape[1], _ptr(y), y.shape[1], None if mi is None else mi.ctypes.data,
+                                       mods.shape[0], _ptr(mods), _ptr(out), _ptr(st))
+        self._check(rc, "tpa_yi")
+        return out, st
+
+    def _tpa_kdf(self, what, call, base, xi, xi_len, exps, salt, mods, mod_idx):
+        base, xi, exps, mods = _u8(base), _u8(xi), _u8(exps), _u8(mods)
+        n, nbytes = base.shape
+        salt = None if salt is None or np.size(salt) == 0 else _u8(salt).reshape(n, -1)
+        salt_len = 0 if salt is None else salt.shape[1]
+        xl = np.ascontiguousarray(xi_len, dtype=np.uint32)
+        mi = None if mod_idx is None else np.ascontiguousarray(mod_idx, dtype=np.uint32)
+        assert xi.shape == base.shape and exps.shape[0] == n and len(xl) == n
+        keys, mac, st = np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        rc, res = call(n, _ptr(base), _ptr(xi), xl.ctypes.data, nbytes, _ptr(exps), exps.shape[1], _ptr(salt), salt_len,
+                       None if mi is None else mi.ctypes.data, mods.shape[0], _ptr(mods), _ptr(keys), _ptr(mac), _ptr(st))
+        self._check(rc, what)
+        return res + (keys, mac, st)
+
+    def tpa_bi(self, v, xi, xi_len, b, salt, mods, mod_idx=None):
+        """makeBi: bi = v ^ b, ki = SetBytes(xi[:xi_len]) ^ b, keys = km | ke of keySched(ki.Bytes(), salt), mac = HMAC(km, xi | bi.Bytes()).
+        v, xi [n, nbytes], xi_len [n], b [n, exp_len], salt [n, salt_len] or None -> (bi [n, nbytes], keys [n, 32], mac [n, 32], status)."""
+        def call(n, pv, pxi, pxl, nbytes, pb, el, ps, sl, pmi, nm, pm, pk, pmac, pst):
+            out = np.zeros((n, nbytes), dtype=np.uint8)
+            return self.lib.bftkv_gpu_tpa_bi(self.h, n, pv, pxi, pxl, nbytes, pb, el, ps, sl, pmi, nm, pm, _ptr(out), pk, pmac, pst), (out,)
+        return self._tpa_kdf("tpa_bi", call, v, xi, xi_len, b, salt, mods, mod_idx)
+
+    def tpa_ni(self, bi, xi, xi_len, e, salt, mods, mod_idx=None):
+        """processBi: ki = bi ^ e, the same keySched, ni = HMAC(km, xi | bi.Bytes()) over the bytes of bi as given
+        -> (keys [n, 32], ni [n, 32], status)."""
+        def call(n, pbi, pxi, pxl, nbytes, pe, el, ps, sl, pmi, nm, pm, pk, pmac, pst):
+            return self.lib.bftkv_gpu_tpa_ni(self.h, n, pbi, pxi, pxl, nbytes, pe, el, ps, sl, pmi, nm, pm, pk, pmac, pst), ()
+        return self._tpa_kdf("tpa_ni", call, bi, xi, xi_len, e, salt, mods, mod_idx)
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -971,6 +1019,24 @@ class Batcher:
         out, st = np.full(nbytes, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
         rc = self.lib.bftkv_gpu_batcher_modexp(self.h, _ptr(b), nbytes, _ptr(e), exp_len, _ptr(m), _ptr(out), _ptr(st))
         return rc, int(st[0]), int.from_bytes(out.tobytes(), "big")
+
+    def tpa_yi(self, x: bytes, y: bytes, mod: bytes):
+        """makeYi for one request: x and mod of nbytes, y of exp_len bytes, big-endian -> (rc, status, yi bytes)."""
+        xx, yy, m = _u8(x), _u8(y), _u8(mod)
+        out, st = np.full(max(1, len(x)), 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_tpa_yi(self.h, _ptr(xx), len(x), _ptr(yy), len(y), _ptr(m), _ptr(out), _ptr(st))
+        return rc, int(st[0]), out[:len(x)].tobytes()
+
+    def tpa_bi(self, v: bytes, xi: bytes, b: bytes, salt: bytes, mod: bytes):
+        """makeBi for one request: v and mod of nbytes, xi as received (at most nbytes), b of exp_len bytes, salt of at most 64
+        -> (rc, status, bi bytes, keys, mac)."""
+        vv, bb, m = _u8(v), _u8(b), _u8(mod)
+        xx, ss = (_u8(xi) if xi else None), (_u8(salt) if salt else None)
+        out, st = np.full(max(1, len(v)), 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        keys, mac = np.full(32, 0xAA, dtype=np.uint8), np.full(32, 0xAA, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_tpa_bi(self.h, _ptr(vv), _ptr(xx), len(xi), len(v), _ptr(bb), len(b), _ptr(ss), len(salt), _ptr(m), _ptr(out),
+                                               _ptr(keys), _ptr(mac), _ptr(st))
+        return rc, int(st[0]), out[:len(v)].tobytes(), keys.tobytes(), mac.tobytes()
 
     def stats(self):
         st = (C.c_uint64 * 4)()

@@ -278,7 +278,8 @@ struct bftkv_gpu_batcher {
   enum class Kind {
     Collective, Signature, Message, Cert,                      // CollectiveSignature.Verify, Signature.Verify, a transport message, Issuer + VerifyWithCertificate
     ModmulProduct, LagrangeCombine, DsaCalculateR, Modexp,     // ONE share-combine operation: prod psig mod N, sum l_j y_j mod m, CalculateR, b^x mod n
-    EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset, RsaVerify, RsaVerifyKeyset
+    EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset, RsaVerify, RsaVerifyKeyset,
+    TpaYi, TpaBi                                               // ONE password-authentication answer of a server: makeYi, makeBi (crypto/auth)
   };
   static bool hashed_by_caller(Kind k) { return k == Kind::Collective || k == Kind::Signature; }      // a SHA-256 midstate of tbs goes to the device, not tbs
   static bool threshold_style(Kind k) { return k >= Kind::ModmulProduct; }      // th_* fields in, a BFTKV_TH_* status byte and th_out out
@@ -300,6 +301,9 @@ struct bftkv_gpu_batcher {
   //   DsaVerifyKeyset           set     dlen  -          -          -      digest          r|s (2 qb)  -       -              -           key     verdict
   //   RsaVerify                 -       dlen  nbytes     hash id    -      digest          s (nbytes)  n       -              -           e       verdict
   //   RsaVerifyKeyset           set     dlen  -          hash id    -      digest          s (nbytes)  -       -              -           key     verdict
+  //   TpaYi                     -       -     nbytes     exp bytes  -      x               y           p       -              -           -       nbytes
+  //   TpaBi                     -       salt  nbytes     exp bytes  -      v               b           p       -              Xi, salt    Xi len  nbytes
+  // (TpaBi: th_k is the salt's length; its keys and MAC, 32 bytes each, go to tpa_keys and tpa_mac.)
   // An EcdsaCalculateR or EcdsaVerify group shares one recognised curve, which the device call takes by value: its bit size is part of
   // the shape.  A key-set group shares the set: the lane is a fork and passes the handle through.
   struct Req {
@@ -336,6 +340,7 @@ struct bftkv_gpu_batcher {
     uint8_t* th_out = nullptr;
     uint32_t ks_key = 0;       // the key's index within the set (RsaVerify: the public exponent)
     const uint8_t *th_g = nullptr, *th_y = nullptr;
+    uint8_t *tpa_keys = nullptr, *tpa_mac = nullptr;
   };
   struct Batch {
     std::vector<Req*> reqs;
@@ -686,6 +691,38 @@ struct bftkv_gpu_batcher {
     publish_outputs(g, rc, st.data(), out.data(), o_w);
   }
 
+  // TpaYi, TpaBi: a group's callers share (nbytes, exp_len, salt_len), whatever their moduli, which make the call's table in BYTE ORDER
+  // as in run_threshold.  A request's Xi and salt are copied at their own lengths into the rows the batched entry takes.
+  void run_tpa(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const bool bi = r0.kind == Kind::TpaBi;
+    const uint32_t n = (uint32_t)g.size(), nb = r0.th_nbytes, el = r0.th_qbytes, sl = r0.th_k;
+    std::map<std::string, uint32_t> slot;
+    for (Req* r : g) slot.emplace(std::string((const char*)r->th_mod, nb), 0u);
+    uint32_t n_mods = 0;
+    std::vector<uint8_t> mods((size_t)slot.size() * nb);
+    for (auto& kv : slot) { kv.second = n_mods; memcpy(&mods[(size_t)n_mods * nb], kv.first.data(), nb); ++n_mods; }
+    const std::vector<uint8_t> a = gather(g, &Req::th_a, nb), e = gather(g, &Req::th_b, el);
+    std::vector<uint8_t> xi(bi ? (size_t)n * nb : 0, 0), salt(bi ? (size_t)n * sl : 0), out((size_t)n * nb), keys((size_t)n * 32), mac((size_t)n * 32),
+        st((size_t)n + 8, BFTKV_TH_FAILED);
+    std::vector<uint32_t> idx(n), xl(bi ? n : 0);
+    for (uint32_t i = 0; i < n; ++i) {
+      idx[i] = slot[std::string((const char*)g[i]->th_mod, nb)];
+      if (!bi) continue;
+      xl[i] = g[i]->ks_key;
+      if (xl[i]) memcpy(&xi[(size_t)i * nb], g[i]->th_g, xl[i]);
+      if (sl) memcpy(&salt[(size_t)i * sl], g[i]->th_y, sl);
+    }
+    const int rc = tpa_impl(lane.ctx, bi ? TpaMode::Bi : TpaMode::Yi, n, a.data(), bi ? xi.data() : nullptr, bi ? xl.data() : nullptr, nb, e.data(), el,
+                            sl ? salt.data() : nullptr, sl, idx.data(), n_mods, mods.data(), out.data(), bi ? keys.data() : nullptr,
+                            bi ? mac.data() : nullptr, st.data());
+    ++device_calls;
+    publish_outputs(g, rc, st.data(), out.data(), nb);
+    if (bi && !rc)
+      for (uint32_t i = 0; i < n; ++i)
+        if (st[i] == BFTKV_TH_OK) { memcpy(g[i]->tpa_keys, &keys[(size_t)i * 32], 32); memcpy(g[i]->tpa_mac, &mac[(size_t)i * 32], 32); }
+  }
+
   // group by (kind, quorum / certificate use, threshold shape): one device call per group
   uint64_t process(Lane& lane, std::vector<Req*>& batch) {
     uint64_t calls = 0;     // device calls made for this batch
@@ -721,6 +758,7 @@ struct bftkv_gpu_batcher {
           });
           break;
         }
+        case Kind::TpaYi: case Kind::TpaBi: run_tpa(lane, g, calls); break;
       }
     }
     return calls;
@@ -1084,6 +1122,37 @@ int bftkv_gpu_batcher_rsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32
   bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::RsaVerifyKeyset, keyset, dlen, hash_id);
   r.th_k = dlen; r.th_qbytes = hash_id; r.th_a = digest; r.th_b = sig; r.th_out = valid_out; r.ks_key = key;
   return verdict_submit(b, r, status_out);
+}
+
+// One answer of a server in the password authentication (crypto/auth): makeYi, makeBi.  What bftkv_gpu_tpa_yi / _bi refuse for the WHOLE
+// call is refused here for this caller alone, before it joins a batch.
+int bftkv_gpu_batcher_tpa_yi(bftkv_gpu_batcher* b, const uint8_t* x, uint32_t nbytes, const uint8_t* y, uint32_t exp_len, const uint8_t* mod,
+                             uint8_t* yi_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (yi_out) memset(yi_out, 0, nbytes);
+  if (!b || !status_out || !yi_out || !x || !y || !mod || !tpa_shape_ok(TpaMode::Yi, nbytes, exp_len, 0)) return BFTKV_E_INVALID;
+  if (!(mod[nbytes - 1] & 1)) return BFTKV_E_UNSUPPORTED;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::TpaYi, bftkv_gpu_batcher::NO_QUORUM, nbytes, exp_len);
+  r.th_nbytes = nbytes; r.th_qbytes = exp_len; r.th_a = x; r.th_b = y; r.th_mod = mod; r.th_out = yi_out;
+  return threshold_submit(b, r, status_out);
+}
+int bftkv_gpu_batcher_tpa_bi(bftkv_gpu_batcher* b, const uint8_t* v, const uint8_t* xi, uint32_t xi_len, uint32_t nbytes, const uint8_t* bexp,
+                             uint32_t exp_len, const uint8_t* salt, uint32_t salt_len, const uint8_t* mod, uint8_t* bi_out, uint8_t* keys_out,
+                             uint8_t* mac_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (bi_out) memset(bi_out, 0, nbytes);
+  if (keys_out) memset(keys_out, 0, 32);
+  if (mac_out) memset(mac_out, 0, 32);
+  if (!b || !status_out || !bi_out || !keys_out || !mac_out || !v || !bexp || !mod || !tpa_shape_ok(TpaMode::Bi, nbytes, exp_len, salt_len) ||
+      xi_len > nbytes || (xi_len && !xi) || (salt_len && !salt))
+    return BFTKV_E_INVALID;
+  if (!(mod[nbytes - 1] & 1)) return BFTKV_E_UNSUPPORTED;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::TpaBi, bftkv_gpu_batcher::NO_QUORUM, nbytes, exp_len, salt_len);
+  r.th_k = salt_len; r.th_nbytes = nbytes; r.th_qbytes = exp_len; r.th_a = v; r.th_b = bexp; r.th_mod = mod; r.th_g = xi; r.th_y = salt; r.ks_key = xi_len;
+  r.th_out = bi_out; r.tpa_keys = keys_out; r.tpa_mac = mac_out;
+  const int rc = threshold_submit(b, r, status_out);
+  if (rc || *status_out != BFTKV_TH_OK) { memset(bi_out, 0, nbytes); memset(keys_out, 0, 32); memset(mac_out, 0, 32); }
+  return rc;
 }
 
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]) {

@@ -38,6 +38,7 @@
 #include "ec_kernels.hip"
 #include "dsa_verify_kernels.hip"
 #include "rsa_verify_kernels.hip"
+#include "tpa_kernels.hip"
 
 using namespace bftkv;
 
@@ -2445,6 +2446,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "dsa_verify_capi.inc"
 #include "dsa_keyset_capi.inc"
 #include "rsa_verify_capi.inc"
+#include "tpa_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

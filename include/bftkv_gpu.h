@@ -428,6 +428,18 @@ int bftkv_gpu_batcher_rsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, ui
  * RUNS: the caller must not destroy a set while calls that name it are in flight. */
 int bftkv_gpu_batcher_rsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t hash_id, uint32_t dlen,
                                         const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
+/* ONE answer of a server in the threshold password authentication (bftkv_gpu_tpa_yi / bftkv_gpu_tpa_bi below; makeYi and makeBi of
+ * crypto/auth/auth.go, driven by Server.authenticate, protocol/server.go:405-448).  x, v, mod and the outputs are [nbytes], y and
+ * bexp [exp_len], big-endian; xi points at the request's xi_len bytes (0 .. nbytes; may be NULL when xi_len is 0) and salt at
+ * salt_len bytes (0 .. 64; may be NULL when salt_len is 0); keys_out and mac_out are 32 bytes each.  Callers are grouped by
+ * (nbytes, exp_len, salt_len), whatever their moduli.  What the batched entries refuse for the whole call returns BFTKV_E_INVALID --
+ * an even modulus BFTKV_E_UNSUPPORTED -- for that caller alone, before it joins a batch.  Whenever the return code is not 0,
+ * *status_out is BFTKV_TH_FAILED and every output byte 0.  The exponents are SECRETS (bftkv_gpu_batcher_modexp). */
+int bftkv_gpu_batcher_tpa_yi(bftkv_gpu_batcher* b, const uint8_t* x, uint32_t nbytes, const uint8_t* y, uint32_t exp_len, const uint8_t* mod,
+                             uint8_t* yi_out, uint8_t* status_out);
+int bftkv_gpu_batcher_tpa_bi(bftkv_gpu_batcher* b, const uint8_t* v, const uint8_t* xi, uint32_t xi_len, uint32_t nbytes, const uint8_t* bexp,
+                             uint32_t exp_len, const uint8_t* salt, uint32_t salt_len, const uint8_t* mod, uint8_t* bi_out, uint8_t* keys_out,
+                             uint8_t* mac_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -752,6 +764,38 @@ int bftkv_gpu_rsa_verify_keyset(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, 
 /* same with the per-signature arrays resident in HBM: nothing is read from host memory, the call never waits */
 int bftkv_gpu_rsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen,
                                     const uint8_t* sigs, const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+
+/* ---- threshold password authentication, TPA (docs/parity.md "Password authentication (crypto/auth)") ------------------------
+ * The phase computations of crypto/auth/auth.go, from request bytes to response fields in one device pass:
+ *   bftkv_gpu_tpa_yi   server, phase 0 (makeYi :196-200)      Yi = SetBytes(x)^y mod p
+ *   bftkv_gpu_tpa_bi   server, phase 1 (makeBi :202-223)      Bi = v^b mod p, Ki = SetBytes(xi)^b mod p, km | ke = keySched(Ki.Bytes(), salt),
+ *                                                            mac = HMAC-SHA256(km, xi | Bi.Bytes())
+ *   bftkv_gpu_tpa_ni   client, phase 1 (processBi :331-347)   Ki = bi^e mod p, the same keySched, Ni = HMAC-SHA256(km, xi | bi.Bytes())
+ * keySched (:182-194) is the first 32 bytes of HKDF-SHA256(secret = Ki.Bytes(), salt, no info): km the first 16, ke the next 16.
+ * .Bytes() is Go's minimal big-endian form: no leading zero bytes, nothing at all for 0.
+ *   x, v, bi [n_ops][nbytes] big-endian, 1 <= nbytes <= 256, ANY value: a base of p or more is reduced as big.Int.Exp reduces it.
+ *   xi [n_ops][nbytes]: the request's xi_len[op] bytes (0 .. nbytes) at the front of the row, AS RECEIVED -- they are the number that
+ *       is raised and, byte for byte, the head of the MAC's input; the rest of the row is ignored.
+ *   y, b, e [n_ops][exp_len] big-endian, 1 <= exp_len <= 256.  They are SECRETS: the sequence of products depends on exp_len alone
+ *       (the address of a table row does depend on an exponent digit); a deployment decides whether they may leave the host.
+ *       An exponent of 0 gives 1 (0 under p = 1), for a base of 0 too.
+ *   salt [n_ops][salt_len], one salt_len (0 .. 64) per call; NULL is accepted when salt_len is 0.
+ *   mod_idx [n_ops] into mods [n_mods][nbytes] (NULL: modulus 0; an index past the table is clamped to its last row); the tables of a
+ *       set of moduli are cached by value, as for the threshold entries.
+ *   yi_out, bi_out [n_ops][nbytes] fixed width (the caller strips them); keys_out [n_ops][32] = km | ke; mac_out [n_ops][32];
+ *   status_out [n_ops]: BFTKV_TH_OK, or BFTKV_TH_FAILED whenever the return code is not 0.
+ * BFTKV_E_INVALID: a NULL context, n_ops 0 or > 2^22, n_mods 0, nbytes or exp_len 0 or > 256, salt_len > 64, an xi_len[op] > nbytes,
+ * a NULL array.  BFTKV_E_UNSUPPORTED: an even modulus in the table.  Whenever the return code is not 0, every status is
+ * BFTKV_TH_FAILED and every byte of the n_ops rows of every output 0.  Nothing is fenced: a request longer than 256 bytes or a salt
+ * longer than 64 is not submitted (the caller keeps the reference path).  The host waits once, after the results' download. */
+int bftkv_gpu_tpa_yi(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* x, uint32_t nbytes, const uint8_t* y, uint32_t exp_len,
+                     const uint32_t* mod_idx, uint32_t n_mods, const uint8_t* mods, uint8_t* yi_out, uint8_t* status_out);
+int bftkv_gpu_tpa_bi(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* v, const uint8_t* xi, const uint32_t* xi_len, uint32_t nbytes,
+                     const uint8_t* b, uint32_t exp_len, const uint8_t* salt, uint32_t salt_len, const uint32_t* mod_idx, uint32_t n_mods,
+                     const uint8_t* mods, uint8_t* bi_out, uint8_t* keys_out, uint8_t* mac_out, uint8_t* status_out);
+int bftkv_gpu_tpa_ni(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* bi, const uint8_t* xi, const uint32_t* xi_len, uint32_t nbytes,
+                     const uint8_t* e, uint32_t exp_len, const uint8_t* salt, uint32_t salt_len, const uint32_t* mod_idx, uint32_t n_mods,
+                     const uint8_t* mods, uint8_t* keys_out, uint8_t* mac_out, uint8_t* status_out);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

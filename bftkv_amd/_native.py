@@ -301,7 +301,7 @@ class Context:
                 "per_piece_us": [{nm: round(v[8 + 10 * k + j], 1) for j, nm in enumerate(names)} for k in range(P)]}
 
     def set_dsa_window_bits(self, bits: int) -> None:
-        """Pin the DSA fixed-base table width (4, 8, 16 .. 20 bits; 0 = default policy); applies at the next keyring_set."""
+        """Pin the DSA fixed-base table width (4 or 8 .. 20 bits; 0 = default policy); applies at the next keyring_set."""
         self._check(self.lib.bftkv_gpu_set_dsa_window_bits(self.h, bits), "set_dsa_window_bits")
 
     def dsa_window_bits(self) -> int:

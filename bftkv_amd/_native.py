@@ -57,6 +57,7 @@ EXPORTS = [
     "bftkv_gpu_rsa_verify", "bftkv_gpu_rsa_verify_dev", "bftkv_gpu_rsa_keyset_create", "bftkv_gpu_rsa_keyset_destroy", "bftkv_gpu_rsa_keyset_info",
     "bftkv_gpu_rsa_verify_keyset", "bftkv_gpu_rsa_verify_keyset_dev", "bftkv_gpu_batcher_rsa_verify", "bftkv_gpu_batcher_rsa_verify_keyset",
     "bftkv_gpu_tpa_yi", "bftkv_gpu_tpa_bi", "bftkv_gpu_tpa_ni", "bftkv_gpu_batcher_tpa_yi", "bftkv_gpu_batcher_tpa_bi",
+    "bftkv_gpu_rsa_partial_sign", "bftkv_gpu_batcher_rsa_partial_sign",
 ]
 
 _lib = None
@@ -181,6 +182,8 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_tpa_ni.argtypes = [vp, u32, u8p, u8p, vp, u32, u8p, u32, u8p, u32, vp, u32, u8p, u8p, u8p, u8p]
     lib.bftkv_gpu_batcher_tpa_yi.argtypes = [vp, u8p, u32, u8p, u32, u8p, u8p, u8p]
     lib.bftkv_gpu_batcher_tpa_bi.argtypes = [vp, u8p, u8p, u32, u32, u8p, u32, u8p, u32, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_rsa_partial_sign.argtypes = [vp, u32, u8p, u32, vp, vp, u32, u8p, u32, u32, vp, u8p, u32, vp, u8p, u8p, u8p]
+    lib.bftkv_gpu_batcher_rsa_partial_sign.argtypes = [vp, u8p, u32, u8p, u32, u32, u8p, u32, vp, u8p, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -835,6 +838,25 @@ class Context:
             return self.lib.bftkv_gpu_tpa_ni(self.h, n, pbi, pxi, pxl, nbytes, pe, el, ps, sl, pmi, nm, pm, pk, pmac, pst), ()
         return self._tpa_kdf("tpa_ni", call, bi, xi, xi_len, e, salt, mods, mod_idx)
 
+    # ---- threshold RSA signing, the server's side (rsaContext.Sign): rows of uint8, big-endian
+    def rsa_partial_sign(self, t, t_len, mods, exps, sign, mod_idx=None, frag_req=None, exp_used=None):
+        """The partial signatures of a batch of sign requests.  t [n_reqs, t_cap] with t_len [n_reqs] bytes at the front of each row,
+        mods [m, nbytes], mod_idx [n_reqs] or None (modulus 0); exps [n_frags, exp_len] right-aligned magnitudes, sign [n_frags] the stored
+        bytes, frag_req [n_frags] or None (request 0), exp_used [n_frags] or None (exp_len) -> (out [n_frags, nbytes], status [n_frags])."""
+        t, mods, exps, sign = _u8(t), _u8(mods), _u8(exps), _u8(sign)
+        tl = np.ascontiguousarray(t_len, dtype=np.uint32)
+        n_reqs, n_frags, nbytes = len(tl), exps.shape[0], mods.shape[1]
+        t = t.reshape(n_reqs, t.size // max(n_reqs, 1))
+        opt = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)      # noqa: E731
+        mi, fr, eu = opt(mod_idx), opt(frag_req), opt(exp_used)
+        assert len(sign) == n_frags and all(a is None or len(a) == n for a, n in ((mi, n_reqs), (fr, n_frags), (eu, n_frags)))
+        addr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+        out, st = np.zeros((n_frags, nbytes), dtype=np.uint8), np.zeros(n_frags, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_rsa_partial_sign(self.h, n_reqs, _ptr(t) if t.shape[1] else None, t.shape[1], tl.ctypes.data, addr(mi), mods.shape[0],
+                                                 _ptr(mods), nbytes, n_frags, addr(fr), _ptr(exps), exps.shape[1], addr(eu), _ptr(sign), _ptr(out), _ptr(st))
+        self._check(rc, "rsa_partial_sign")
+        return out, st
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -1037,6 +1059,18 @@ class Batcher:
         rc = self.lib.bftkv_gpu_batcher_tpa_bi(self.h, _ptr(vv), _ptr(xx), len(xi), len(v), _ptr(bb), len(b), _ptr(ss), len(salt), _ptr(m), _ptr(out),
                                                _ptr(keys), _ptr(mac), _ptr(st))
         return rc, int(st[0]), out[:len(v)].tobytes(), keys.tobytes(), mac.tobytes()
+
+    def rsa_partial_sign(self, t: bytes, mod: bytes, exps, sign, exp_used=None):
+        """rsaContext.Sign for one request with all its fragments: T as received, mod of nbytes, exps [n_frags, exp_len] right-aligned,
+        sign [n_frags], exp_used [n_frags] or None -> (rc, status [n_frags], out [n_frags, nbytes])."""
+        tt, m, ee, sg = (_u8(t) if t else None), _u8(mod), _u8(exps), _u8(sign)
+        n_frags, nbytes = len(sg), len(mod)
+        ee = ee.reshape(max(n_frags, 1), -1)
+        eu = None if exp_used is None else np.ascontiguousarray(exp_used, dtype=np.uint32)
+        out, st = np.full((max(1, n_frags), max(1, nbytes)), 0xAA, dtype=np.uint8), np.zeros(max(1, n_frags), dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_rsa_partial_sign(self.h, _ptr(tt), len(t), _ptr(m), nbytes, n_frags, _ptr(ee), ee.shape[1],
+                                                         None if eu is None else eu.ctypes.data, _ptr(sg), _ptr(out), _ptr(st))
+        return rc, st[:n_frags].copy(), out.reshape(-1)[:n_frags * nbytes].reshape(n_frags, nbytes).copy()
 
     def stats(self):
         st = (C.c_uint64 * 4)()

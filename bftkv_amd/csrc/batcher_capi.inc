@@ -279,7 +279,8 @@ struct bftkv_gpu_batcher {
     Collective, Signature, Message, Cert,                      // CollectiveSignature.Verify, Signature.Verify, a transport message, Issuer + VerifyWithCertificate
     ModmulProduct, LagrangeCombine, DsaCalculateR, Modexp,     // ONE share-combine operation: prod psig mod N, sum l_j y_j mod m, CalculateR, b^x mod n
     EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset, RsaVerify, RsaVerifyKeyset,
-    TpaYi, TpaBi                                               // ONE password-authentication answer of a server: makeYi, makeBi (crypto/auth)
+    TpaYi, TpaBi,                                              // ONE password-authentication answer of a server: makeYi, makeBi (crypto/auth)
+    RsaPartialSign                                             // ONE threshold-RSA sign request of a server with all its fragments: rsaContext.Sign
   };
   static bool hashed_by_caller(Kind k) { return k == Kind::Collective || k == Kind::Signature; }      // a SHA-256 midstate of tbs goes to the device, not tbs
   static bool threshold_style(Kind k) { return k >= Kind::ModmulProduct; }      // th_* fields in, a BFTKV_TH_* status byte and th_out out
@@ -303,7 +304,9 @@ struct bftkv_gpu_batcher {
   //   RsaVerifyKeyset           set     dlen  -          hash id    -      digest          s (nbytes)  -       -              -           key     verdict
   //   TpaYi                     -       -     nbytes     exp bytes  -      x               y           p       -              -           -       nbytes
   //   TpaBi                     -       salt  nbytes     exp bytes  -      v               b           p       -              Xi, salt    Xi len  nbytes
+  //   RsaPartialSign            -       frags nbytes     exp bytes  -      T               magnitudes  N       -              -           T len   frags x nbytes
   // (TpaBi: th_k is the salt's length; its keys and MAC, 32 bytes each, go to tpa_keys and tpa_mac.)
+  // (RsaPartialSign: th_k is the request's fragment count; ps_used and ps_sign are its widths and sign bytes, ps_status its status bytes.)
   // An EcdsaCalculateR or EcdsaVerify group shares one recognised curve, which the device call takes by value: its bit size is part of
   // the shape.  A key-set group shares the set: the lane is a fork and passes the handle through.
   struct Req {
@@ -341,6 +344,7 @@ struct bftkv_gpu_batcher {
     uint32_t ks_key = 0;       // the key's index within the set (RsaVerify: the public exponent)
     const uint8_t *th_g = nullptr, *th_y = nullptr;
     uint8_t *tpa_keys = nullptr, *tpa_mac = nullptr;
+    const uint32_t* ps_used = nullptr; const uint8_t* ps_sign = nullptr; uint8_t* ps_status = nullptr;
   };
   struct Batch {
     std::vector<Req*> reqs;
@@ -723,6 +727,42 @@ struct bftkv_gpu_batcher {
         if (st[i] == BFTKV_TH_OK) { memcpy(g[i]->tpa_keys, &keys[(size_t)i * 32], 32); memcpy(g[i]->tpa_mac, &mac[(size_t)i * 32], 32); }
   }
 
+  // RsaPartialSign: a group's callers share (nbytes, exp_len), whatever their moduli (the call's table, in BYTE ORDER as in run_threshold),
+  // fragment counts and T lengths: every caller is one request of the call, its fragments rows of the call's fragment arrays.
+  void run_psign(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), nb = r0.th_nbytes, el = r0.th_qbytes;
+    std::map<std::string, uint32_t> slot;
+    for (Req* r : g) slot.emplace(std::string((const char*)r->th_mod, nb), 0u);
+    uint32_t n_mods = 0, t_cap = 0, n_frags = 0;
+    std::vector<uint8_t> mods((size_t)slot.size() * nb);
+    for (auto& kv : slot) { kv.second = n_mods; memcpy(&mods[(size_t)n_mods * nb], kv.first.data(), nb); ++n_mods; }
+    for (Req* r : g) { t_cap = std::max(t_cap, r->ks_key); n_frags += r->th_k; }
+    std::vector<uint8_t> t((size_t)n * t_cap + 1, 0), e((size_t)n_frags * el), sg(n_frags), out((size_t)n_frags * nb), st((size_t)n_frags + 8, BFTKV_TH_FAILED);
+    std::vector<uint32_t> idx(n), tl(n), fr(n_frags), used(n_frags);
+    uint32_t f = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const Req* r = g[i];
+      idx[i] = slot[std::string((const char*)r->th_mod, nb)];
+      tl[i] = r->ks_key;
+      if (tl[i]) memcpy(&t[(size_t)i * t_cap], r->th_a, tl[i]);
+      memcpy(&e[(size_t)f * el], r->th_b, (size_t)r->th_k * el);
+      memcpy(&sg[f], r->ps_sign, r->th_k);
+      for (uint32_t j = 0; j < r->th_k; ++j) { fr[f + j] = i; used[f + j] = r->ps_used ? r->ps_used[j] : el; }
+      f += r->th_k;
+    }
+    const int rc = psign_impl(lane.ctx, n, t.data(), t_cap, tl.data(), idx.data(), n_mods, mods.data(), nb, n_frags, fr.data(), e.data(), el, used.data(),
+                              sg.data(), out.data(), st.data());
+    ++device_calls;
+    f = 0;
+    for (Req* r : g) {
+      r->rc = rc;
+      r->err = rc ? Req::failing(r->kind) : (uint8_t)BFTKV_TH_OK;
+      if (!rc) { memcpy(r->th_out, &out[(size_t)f * nb], (size_t)r->th_k * nb); memcpy(r->ps_status, &st[f], r->th_k); }
+      f += r->th_k;
+    }
+  }
+
   // group by (kind, quorum / certificate use, threshold shape): one device call per group
   uint64_t process(Lane& lane, std::vector<Req*>& batch) {
     uint64_t calls = 0;     // device calls made for this batch
@@ -759,6 +799,7 @@ struct bftkv_gpu_batcher {
           break;
         }
         case Kind::TpaYi: case Kind::TpaBi: run_tpa(lane, g, calls); break;
+        case Kind::RsaPartialSign: run_psign(lane, g, calls); break;
       }
     }
     return calls;
@@ -1152,6 +1193,29 @@ int bftkv_gpu_batcher_tpa_bi(bftkv_gpu_batcher* b, const uint8_t* v, const uint8
   r.th_out = bi_out; r.tpa_keys = keys_out; r.tpa_mac = mac_out;
   const int rc = threshold_submit(b, r, status_out);
   if (rc || *status_out != BFTKV_TH_OK) { memset(bi_out, 0, nbytes); memset(keys_out, 0, 32); memset(mac_out, 0, 32); }
+  return rc;
+}
+
+// ONE sign request of a threshold-RSA server (rsaContext.Sign) with all its fragments.  What bftkv_gpu_rsa_partial_sign refuses for the
+// WHOLE call is refused here for this caller alone, before it joins a batch.
+int bftkv_gpu_batcher_rsa_partial_sign(bftkv_gpu_batcher* b, const uint8_t* t, uint32_t t_len, const uint8_t* mod, uint32_t nbytes, uint32_t n_frags,
+                                       const uint8_t* exps, uint32_t exp_len, const uint32_t* exp_used, const uint8_t* sign, uint8_t* out,
+                                       uint8_t* status_out) {
+  const bool counted = n_frags != 0 && n_frags <= PSIGN_BATCHER_FRAGS;
+  const PsignOut o{out, status_out, counted ? n_frags : 0u, nbytes};
+  o.fail_closed();
+  if (!b || !counted || !status_out || !out || !mod || !exps || !sign || !psign_shape_ok(nbytes, exp_len, t_len) || (t_len && !t)) return BFTKV_E_INVALID;
+  {
+    std::vector<uint32_t> used(n_frags);
+    std::vector<uint8_t> negative(n_frags);
+    if (!psign_frags_ok(n_frags, exps, exp_len, exp_used, sign, used.data(), negative.data())) return BFTKV_E_INVALID;
+  }
+  if (!(mod[nbytes - 1] & 1) && !psign_all_zero(mod, nbytes)) return BFTKV_E_UNSUPPORTED;      // (N = 0 is a refused request, not an even modulus)
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::RsaPartialSign, bftkv_gpu_batcher::NO_QUORUM, nbytes, exp_len);
+  r.th_k = n_frags; r.th_nbytes = nbytes; r.th_qbytes = exp_len; r.th_a = t; r.ks_key = t_len; r.th_b = exps; r.th_mod = mod; r.th_out = out;
+  r.ps_used = exp_used; r.ps_sign = sign; r.ps_status = status_out;
+  const int rc = b->submit(r);
+  if (rc) o.fail_closed();
   return rc;
 }
 

@@ -39,6 +39,7 @@
 #include "dsa_verify_kernels.hip"
 #include "rsa_verify_kernels.hip"
 #include "tpa_kernels.hip"
+#include "rsa_psign_kernels.hip"
 
 using namespace bftkv;
 
@@ -228,6 +229,7 @@ struct bftkv_gpu_ctx {
   uint32_t multiexp_lanes = 0;        // experiment knob (BFTKV_MULTIEXP_LANES = 4 | 8): lanes per number in k_multiexp, 0 = by call size
   uint32_t rsav_lanes = 0;            // experiment knob (BFTKV_RSAV_LANES = 4 | 8): lanes per signature in k_rsav_verify, 0 = by call size
   uint32_t dsa_inv_mode = 0;          // experiment knob (BFTKV_DSA_INV = single | batched): 1 / 2, 0 = by batch shape
+  bool psign_caller_order = false;    // experiment knob (BFTKV_PSIGN_ORDER = caller): k_psign_pow's chains as submitted, not longest first
   uint32_t n_cus = 256;               // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   uint32_t lagrange_x_bound = 0;      // bftkv_gpu_set_lagrange_x_bound: device-resident callers promise 0 <= x <= bound (0: no promise)
   bool early_exit = true;              // CollectiveSignature.Verify stops verifying where the reference stops reading (bftkv_gpu_set_early_exit)
@@ -1347,6 +1349,7 @@ int bftkv_gpu_init(int device_ordinal, bftkv_gpu_ctx** out) {
   if (const char* e = getenv("BFTKV_RSAV_LANES")) c->rsav_lanes = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_MULTIEXP_BLOCK")) c->multiexp_block = (uint32_t)atoi(e);
   if (const char* e = getenv("BFTKV_DSA_INV")) c->dsa_inv_mode = !strcmp(e, "batched") ? 2u : !strcmp(e, "single") ? 1u : 0u;
+  if (const char* e = getenv("BFTKV_PSIGN_ORDER")) c->psign_caller_order = !strcmp(e, "caller");
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_ordinal) == hipSuccess && cus > 0) c->n_cus = (uint32_t)cus; }
   *out = c;
   return BFTKV_OK;
@@ -2447,6 +2450,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "dsa_keyset_capi.inc"
 #include "rsa_verify_capi.inc"
 #include "tpa_capi.inc"
+#include "rsa_psign_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

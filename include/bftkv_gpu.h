@@ -440,6 +440,16 @@ int bftkv_gpu_batcher_tpa_yi(bftkv_gpu_batcher* b, const uint8_t* x, uint32_t nb
 int bftkv_gpu_batcher_tpa_bi(bftkv_gpu_batcher* b, const uint8_t* v, const uint8_t* xi, uint32_t xi_len, uint32_t nbytes, const uint8_t* bexp,
                              uint32_t exp_len, const uint8_t* salt, uint32_t salt_len, const uint8_t* mod, uint8_t* bi_out, uint8_t* keys_out,
                              uint8_t* mac_out, uint8_t* status_out);
+/* ONE sign request of a threshold-RSA server, with ALL its fragments (bftkv_gpu_rsa_partial_sign below; rsaContext.Sign, driven by
+ * Server.distSign, protocol/server.go:528-541).  t points at the request's t_len bytes (0 .. nbytes; may be NULL when t_len is 0),
+ * mod is [nbytes], exps [n_frags][exp_len] right-aligned with exp_used [n_frags] (NULL: exp_len), sign [n_frags], out
+ * [n_frags][nbytes], status_out [n_frags]; 1 <= n_frags <= 4096.  Callers are grouped by (nbytes, exp_len), whatever their moduli,
+ * fragment counts and T lengths.  What the batched entry refuses for the whole call returns BFTKV_E_INVALID -- an even modulus
+ * BFTKV_E_UNSUPPORTED -- for that caller alone, before it joins a batch.  Whenever the return code is not 0, every status is
+ * BFTKV_TH_FAILED and every output byte 0.  The fragments are SECRETS (bftkv_gpu_rsa_partial_sign). */
+int bftkv_gpu_batcher_rsa_partial_sign(bftkv_gpu_batcher* b, const uint8_t* t, uint32_t t_len, const uint8_t* mod, uint32_t nbytes, uint32_t n_frags,
+                                       const uint8_t* exps, uint32_t exp_len, const uint32_t* exp_used, const uint8_t* sign, uint8_t* out,
+                                       uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -796,6 +806,40 @@ int bftkv_gpu_tpa_bi(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* v, const
 int bftkv_gpu_tpa_ni(bftkv_gpu_ctx* ctx, uint32_t n_ops, const uint8_t* bi, const uint8_t* xi, const uint32_t* xi_len, uint32_t nbytes,
                      const uint8_t* e, uint32_t exp_len, const uint8_t* salt, uint32_t salt_len, const uint32_t* mod_idx, uint32_t n_mods,
                      const uint8_t* mods, uint8_t* keys_out, uint8_t* mac_out, uint8_t* status_out);
+
+/* ---- threshold RSA signing, the server's side (docs/parity.md "Threshold RSA signing (rsaContext.Sign)") ----------------------
+ * rsaContext.Sign (crypto/threshold/rsa/rsa.go:140-178) from request bytes and stored key fragments to the partial signatures of
+ * serializePartialSignature, in one device pass.  A REQUEST is T = prefix | digest as parseHashInfo delivers it (any bytes, any
+ * length: Sign does not look inside), a modulus N of the call's table, and one or more FRAGMENTS, each a sign byte and a magnitude as
+ * parsePartialParam reads them (:457-469).  With emlen = ceil(bits(N) / 8), in this order:
+ *   emlen - len(T) < 3 (N = 1, and N = 0 as a row of zeroes, included)     every fragment of the request BFTKV_TH_INVALID_INPUT (the
+ *                                                                          reference returns crypto.ErrInvalidInput), output zero
+ *   otherwise m = 00 01 FF .. 00 | T as an integer, emlen - len(T) - 3 bytes of FF (none at all when that is 0); m < N always
+ *   sign byte != 0, magnitude != 0, gcd(m, N) != 1                         BFTKV_TH_NO_INVERSE, output zero (ModInverse returns nil: take
+ *                                                                          the reference path)
+ *   sign byte != 0, magnitude != 0                                         (m^magnitude)^-1 mod N, BFTKV_TH_OK
+ *   anything else (sign byte 0; magnitude 0 under any sign byte)           m^magnitude mod N (1 for magnitude 0), BFTKV_TH_OK
+ * The index kid * n + id + 1, the lookup of params.keys[kid] and the serialising stay with the caller.
+ *   t [n_reqs][t_cap], the request's t_len[r] bytes (0 .. t_cap <= nbytes) at the front of its row; NULL is accepted when t_cap is 0.
+ *   mod_idx [n_reqs] into mods [n_mods][nbytes] (NULL: modulus 0; an index past the table is clamped to its last row), 1 <= nbytes <= 256.
+ *   frag_req [n_frags]: the request a fragment belongs to (NULL: request 0; an index past the requests is clamped to the last).
+ *   exps [n_frags][exp_len], big-endian and right-aligned, 1 <= exp_len <= 8200; exp_used [n_frags] (NULL: exp_len): the bytes at a
+ *       row's end that hold its magnitude -- what lies ahead of them must be zero.  A fragment costs as many products as the widest of
+ *       the 16 chains it shares a wave with (10 per byte), and the chains of a call are ordered by exp_used: pass the true widths.
+ *   sign [n_frags]: the stored byte (any non-zero value negates).
+ *   out [n_frags][nbytes] fixed width (the caller strips it to .Bytes()); status_out [n_frags] as above, or BFTKV_TH_FAILED.
+ * The magnitudes and sign bytes are SECRET shares: given the widths, the sequence of products does not depend on them (the address of
+ * a table row does depend on a digit, that of the base row, m or m^-1, on the sign); the widths follow from a fragment's depth in the
+ * key tree, which its index discloses.  A deployment decides whether they may leave the host.
+ * BFTKV_E_INVALID: a NULL context, n_reqs, n_frags or n_mods 0 (or a count > 2^22), nbytes 0 or > 256, exp_len 0 or > 8200, t_cap >
+ * nbytes, a t_len[r] > t_cap, an exp_used[f] > exp_len, a row with a non-zero byte ahead of its last exp_used[f] bytes, a NULL array
+ * that is not optional.  BFTKV_E_UNSUPPORTED: an even modulus in the table (other than N = 0).  Whenever the return code is not 0,
+ * every status is BFTKV_TH_FAILED and every output byte 0.  The host waits once, after the results' download. */
+#define BFTKV_TH_INVALID_INPUT 3
+int bftkv_gpu_rsa_partial_sign(bftkv_gpu_ctx* ctx, uint32_t n_reqs, const uint8_t* t, uint32_t t_cap, const uint32_t* t_len,
+                               const uint32_t* mod_idx, uint32_t n_mods, const uint8_t* mods, uint32_t nbytes, uint32_t n_frags,
+                               const uint32_t* frag_req, const uint8_t* exps, uint32_t exp_len, const uint32_t* exp_used, const uint8_t* sign,
+                               uint8_t* out, uint8_t* status_out);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

@@ -58,6 +58,8 @@ EXPORTS = [
     "bftkv_gpu_rsa_verify_keyset", "bftkv_gpu_rsa_verify_keyset_dev", "bftkv_gpu_batcher_rsa_verify", "bftkv_gpu_batcher_rsa_verify_keyset",
     "bftkv_gpu_tpa_yi", "bftkv_gpu_tpa_bi", "bftkv_gpu_tpa_ni", "bftkv_gpu_batcher_tpa_yi", "bftkv_gpu_batcher_tpa_bi",
     "bftkv_gpu_rsa_partial_sign", "bftkv_gpu_batcher_rsa_partial_sign",
+    "bftkv_gpu_tdsa_share", "bftkv_gpu_tdsa_share_dev", "bftkv_gpu_tecdsa_share", "bftkv_gpu_tecdsa_share_dev", "bftkv_gpu_tsig_partial_s",
+    "bftkv_gpu_batcher_tdsa_share", "bftkv_gpu_batcher_tecdsa_share",
 ]
 
 _lib = None
@@ -184,6 +186,13 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_batcher_tpa_bi.argtypes = [vp, u8p, u8p, u32, u32, u8p, u32, u8p, u32, u8p, u8p, u8p, u8p, u8p]
     lib.bftkv_gpu_rsa_partial_sign.argtypes = [vp, u32, u8p, u32, vp, vp, u32, u8p, u32, u32, vp, u8p, u32, vp, u8p, u8p, u8p]
     lib.bftkv_gpu_batcher_rsa_partial_sign.argtypes = [vp, u8p, u32, u8p, u32, u32, u8p, u32, vp, u8p, u8p, u8p]
+    lib.bftkv_gpu_tdsa_share.argtypes = [vp, C.c_int, u32, vp, u32, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_tdsa_share_dev.argtypes = lib.bftkv_gpu_tdsa_share.argtypes
+    lib.bftkv_gpu_tecdsa_share.argtypes = [vp, u32, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_tecdsa_share_dev.argtypes = lib.bftkv_gpu_tecdsa_share.argtypes
+    lib.bftkv_gpu_tsig_partial_s.argtypes = [vp, u32, u8p, u8p, u8p, u8p, u8p, u32, vp, u32, u8p, u8p, u8p]
+    lib.bftkv_gpu_batcher_tdsa_share.argtypes = [vp, C.c_int, u32, u32, u8p, u32, u32, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_batcher_tecdsa_share.argtypes = [vp, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -857,6 +866,47 @@ class Context:
         self._check(rc, "rsa_partial_sign")
         return out, st
 
+    # ---- threshold DSA / ECDSA signing, the server's side (dsaContext.Sign): rows of uint8, big-endian
+    def tdsa_share(self, keyset: int, shares, group_idx=None):
+        """Phase 2 under a resident DSA key set: shares [n_reqs, m, 4, qbytes] (k, a, b, c of every share), group_idx [n_reqs] or None
+        (group 0) -> (ri [n_reqs, pbytes], vi, ki, ci [n_reqs, qbytes], status [n_reqs])."""
+        info = self.dsa_keyset_info(keyset)
+        sh = _u8(shares)
+        n, m = sh.shape[0], sh.shape[1]
+        assert sh.shape[2:] == (4, info["qbytes"])
+        gi = None if group_idx is None else np.ascontiguousarray(group_idx, dtype=np.uint32)
+        assert gi is None or len(gi) == n
+        ri = np.zeros((n, info["pbytes"]), dtype=np.uint8)
+        vi, ki, ci = (np.zeros((n, info["qbytes"]), dtype=np.uint8) for _ in range(3))
+        st = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_tdsa_share(self.h, keyset, n, None if gi is None else gi.ctypes.data, m, _ptr(sh), _ptr(ri), _ptr(vi), _ptr(ki),
+                                                  _ptr(ci), _ptr(st)), "tdsa_share")
+        return ri, vi, ki, ci, st
+
+    def tecdsa_share(self, shares, curve):
+        """Phase 2 on a recognised curve: shares [n_reqs, m, 4, fbytes] -> (ri [n_reqs, 1 + 2 fbytes], vi, ki, ci [n_reqs, fbytes], status)."""
+        cb, bits, f = _curve_bytes(curve)
+        sh = _u8(shares)
+        n, m = sh.shape[0], sh.shape[1]
+        assert sh.shape[2:] == (4, f)
+        ri = np.zeros((n, 1 + 2 * f), dtype=np.uint8)
+        vi, ki, ci = (np.zeros((n, f), dtype=np.uint8) for _ in range(3))
+        st = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_tecdsa_share(self.h, n, m, _ptr(sh), _ptr(cb), bits, _ptr(ri), _ptr(vi), _ptr(ki), _ptr(ci), _ptr(st)), "tecdsa_share")
+        return ri, vi, ki, ci, st
+
+    def tsig_partial_s(self, m_in, r, y, k, c, q, mod_idx=None):
+        """Phase 3 for both schemes: m_in, r, y, k, c [n_reqs, nbytes], q [n_mods, nbytes], mod_idx [n_reqs] or None (modulus 0)
+        -> (si [n_reqs, nbytes], status [n_reqs])."""
+        mm, rr, yy, kk, cc, qq = (_u8(a) for a in (m_in, r, y, k, c, q))
+        n, nbytes = rr.shape
+        assert all(a.shape == (n, nbytes) for a in (mm, yy, kk, cc)) and qq.shape[1] == nbytes
+        mi = None if mod_idx is None else np.ascontiguousarray(mod_idx, dtype=np.uint32)
+        si, st = np.zeros((n, nbytes), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_tsig_partial_s(self.h, n, _ptr(mm), _ptr(rr), _ptr(yy), _ptr(kk), _ptr(cc), nbytes,
+                                                      None if mi is None else mi.ctypes.data, qq.shape[0], _ptr(qq), _ptr(si), _ptr(st)), "tsig_partial_s")
+        return si, st
+
 
 class Batcher:
     """bftkv_gpu_batcher: blocking one-message calls from many threads, aggregated into device batches."""
@@ -1071,6 +1121,28 @@ class Batcher:
         rc = self.lib.bftkv_gpu_batcher_rsa_partial_sign(self.h, _ptr(tt), len(t), _ptr(m), nbytes, n_frags, _ptr(ee), ee.shape[1],
                                                          None if eu is None else eu.ctypes.data, _ptr(sg), _ptr(out), _ptr(st))
         return rc, st[:n_frags].copy(), out.reshape(-1)[:n_frags * nbytes].reshape(n_frags, nbytes).copy()
+
+    def tdsa_share(self, keyset: int, group: int, shares):
+        """dsaContext.Sign, phase 2, for one request under group `group` of a resident DSA key set: shares [m, 4, qbytes]
+        -> (rc, status, ri, vi, ki, ci) as bytes."""
+        info = self.ctx.dsa_keyset_info(keyset)
+        pb, qb = info["pbytes"], info["qbytes"]
+        sh = np.ascontiguousarray(shares, dtype=np.uint8)
+        m, sh = sh.shape[0], _u8(sh.reshape(-1, 4, qb))
+        ri, st = np.full(pb, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        vi, ki, ci = (np.full(qb, 0xAA, dtype=np.uint8) for _ in range(3))
+        rc = self.lib.bftkv_gpu_batcher_tdsa_share(self.h, keyset, group, m, _ptr(sh), pb, qb, _ptr(ri), _ptr(vi), _ptr(ki), _ptr(ci), _ptr(st))
+        return rc, int(st[0]), ri.tobytes(), vi.tobytes(), ki.tobytes(), ci.tobytes()
+
+    def tecdsa_share(self, shares, curve):
+        """dsaContext.Sign, phase 2, for one request on a recognised curve: shares [m, 4, fbytes] -> (rc, status, ri, vi, ki, ci) as bytes."""
+        cb, bits, f = _curve_bytes(curve)
+        sh = np.ascontiguousarray(shares, dtype=np.uint8)
+        m, sh = sh.shape[0], _u8(sh.reshape(-1, 4, f))
+        ri, st = np.full(1 + 2 * f, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        vi, ki, ci = (np.full(f, 0xAA, dtype=np.uint8) for _ in range(3))
+        rc = self.lib.bftkv_gpu_batcher_tecdsa_share(self.h, m, _ptr(sh), _ptr(cb), bits, _ptr(ri), _ptr(vi), _ptr(ki), _ptr(ci), _ptr(st))
+        return rc, int(st[0]), ri.tobytes(), vi.tobytes(), ki.tobytes(), ci.tobytes()
 
     def stats(self):
         st = (C.c_uint64 * 4)()

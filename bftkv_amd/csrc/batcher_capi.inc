@@ -280,7 +280,8 @@ struct bftkv_gpu_batcher {
     ModmulProduct, LagrangeCombine, DsaCalculateR, Modexp,     // ONE share-combine operation: prod psig mod N, sum l_j y_j mod m, CalculateR, b^x mod n
     EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset, RsaVerify, RsaVerifyKeyset,
     TpaYi, TpaBi,                                              // ONE password-authentication answer of a server: makeYi, makeBi (crypto/auth)
-    RsaPartialSign                                             // ONE threshold-RSA sign request of a server with all its fragments: rsaContext.Sign
+    RsaPartialSign,                                            // ONE threshold-RSA sign request of a server with all its fragments: rsaContext.Sign
+    TdsaShare, TecdsaShare                                     // ONE threshold DSA / ECDSA sign request of a server with its m shares: dsaContext.Sign, phase 2
   };
   static bool hashed_by_caller(Kind k) { return k == Kind::Collective || k == Kind::Signature; }      // a SHA-256 midstate of tbs goes to the device, not tbs
   static bool threshold_style(Kind k) { return k >= Kind::ModmulProduct; }      // th_* fields in, a BFTKV_TH_* status byte and th_out out
@@ -305,8 +306,12 @@ struct bftkv_gpu_batcher {
   //   TpaYi                     -       -     nbytes     exp bytes  -      x               y           p       -              -           -       nbytes
   //   TpaBi                     -       salt  nbytes     exp bytes  -      v               b           p       -              Xi, salt    Xi len  nbytes
   //   RsaPartialSign            -       frags nbytes     exp bytes  -      T               magnitudes  N       -              -           T len   frags x nbytes
+  //   TdsaShare                 set     m     pb         qb         -      m shares (4 qb) -           -       -              -           group   1 x pb
+  //   TecdsaShare               -       m     f          bit size   -      m shares (4 f)  -           curve   -              -           -       1 x (1 + 2 f)
   // (TpaBi: th_k is the salt's length; its keys and MAC, 32 bytes each, go to tpa_keys and tpa_mac.)
   // (RsaPartialSign: th_k is the request's fragment count; ps_used and ps_sign are its widths and sign bytes, ps_status its status bytes.)
+  // (TdsaShare, TecdsaShare: th_out is ri; vi, ki and ci go to ts_vi, ts_ki and ts_ci, qb or f bytes each.  TdsaShare's pb and qb are the
+  // caller's word for the set's widths: a group whose word the set does not bear out is refused.)
   // An EcdsaCalculateR or EcdsaVerify group shares one recognised curve, which the device call takes by value: its bit size is part of
   // the shape.  A key-set group shares the set: the lane is a fork and passes the handle through.
   struct Req {
@@ -345,6 +350,7 @@ struct bftkv_gpu_batcher {
     const uint8_t *th_g = nullptr, *th_y = nullptr;
     uint8_t *tpa_keys = nullptr, *tpa_mac = nullptr;
     const uint32_t* ps_used = nullptr; const uint8_t* ps_sign = nullptr; uint8_t* ps_status = nullptr;
+    uint8_t *ts_vi = nullptr, *ts_ki = nullptr, *ts_ci = nullptr;
   };
   struct Batch {
     std::vector<Req*> reqs;
@@ -763,6 +769,41 @@ struct bftkv_gpu_batcher {
     }
   }
 
+  // TdsaShare, TecdsaShare: a group's callers share (set or curve, m) and the widths; every caller is one request of the call.  For a
+  // set, the lane holds its hold on the root's tables from the look at the set to the end of the device call (run_verify_keyset).
+  void run_tsig_share(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const bool dsa = r0.kind == Kind::TdsaShare;
+    const uint32_t n = (uint32_t)g.size(), m = r0.th_k;
+    const size_t qw = dsa ? r0.th_qbytes : r0.th_nbytes, rw = dsa ? r0.th_nbytes : 1 + 2 * (size_t)r0.th_nbytes;
+    const std::vector<uint8_t> sh = gather(g, &Req::th_a, (size_t)m * 4 * qw);
+    std::vector<uint8_t> ri((size_t)n * rw), vi((size_t)n * qw), ki((size_t)n * qw), ci((size_t)n * qw), st((size_t)n + 8, BFTKV_TH_FAILED);
+    int rc;
+    if (dsa) {
+      std::vector<uint32_t> idx(n);
+      for (uint32_t i = 0; i < n; ++i) idx[i] = g[i]->ks_key;
+      ctx_lock lk(lane.ctx->mu);
+      KtRead kr(lane.ctx);
+      const DsaKeySet* ks = kr.rc ? nullptr : KeySets<DsaKeySet>::find(lane.ctx, r0.quorum);
+      if (kr.rc) rc = kr.rc;
+      else if (!ks || ks->pbytes != r0.th_nbytes || ks->qbytes != r0.th_qbytes) rc = BFTKV_E_INVALID;
+      else {
+        rc = tdsa_share_impl(lane.ctx, r0.quorum, n, idx.data(), m, sh.data(), ri.data(), vi.data(), ki.data(), ci.data(), st.data(), false);
+        ++device_calls;
+      }
+    } else {
+      rc = tecdsa_share_impl(lane.ctx, n, m, sh.data(), r0.th_mod, r0.th_qbytes, ri.data(), vi.data(), ki.data(), ci.data(), st.data(), false);
+      ++device_calls;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(r->kind) : st[i];
+      if (rc) continue;
+      memcpy(r->th_out, &ri[i * rw], rw); memcpy(r->ts_vi, &vi[i * qw], qw); memcpy(r->ts_ki, &ki[i * qw], qw); memcpy(r->ts_ci, &ci[i * qw], qw);
+    }
+  }
+
   // group by (kind, quorum / certificate use, threshold shape): one device call per group
   uint64_t process(Lane& lane, std::vector<Req*>& batch) {
     uint64_t calls = 0;     // device calls made for this batch
@@ -800,6 +841,7 @@ struct bftkv_gpu_batcher {
         }
         case Kind::TpaYi: case Kind::TpaBi: run_tpa(lane, g, calls); break;
         case Kind::RsaPartialSign: run_psign(lane, g, calls); break;
+        case Kind::TdsaShare: case Kind::TecdsaShare: run_tsig_share(lane, g, calls); break;
       }
     }
     return calls;
@@ -1217,6 +1259,37 @@ int bftkv_gpu_batcher_rsa_partial_sign(bftkv_gpu_batcher* b, const uint8_t* t, u
   const int rc = b->submit(r);
   if (rc) o.fail_closed();
   return rc;
+}
+
+// ONE sign request of a threshold DSA / ECDSA server (dsaContext.Sign, phase 2) with its m shares.  What the batched entries refuse for
+// the WHOLE call is refused here for this caller alone, before it joins a batch.
+static int tsig_share_submit(bftkv_gpu_batcher* b, bftkv_gpu_batcher::Req& r, const TsigOut& o) {
+  r.th_out = o.ri; r.ts_vi = o.vi; r.ts_ki = o.ki; r.ts_ci = o.ci;
+  const int rc = threshold_submit(b, r, o.st);
+  if (rc) (void)o.fail_closed(nullptr);
+  return rc;
+}
+int bftkv_gpu_batcher_tdsa_share(bftkv_gpu_batcher* b, int dsa_keyset, uint32_t group_idx, uint32_t m, const uint8_t* shares, uint32_t pbytes,
+                                 uint32_t qbytes, uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out) {
+  const bool sized = pbytes != 0 && pbytes <= 256 && qbytes != 0 && qbytes <= 32;
+  const TsigOut o{ri_out, vi_out, ki_out, ci_out, status_out, 1, sized ? pbytes : 0u, sized ? qbytes : 0u, false};
+  (void)o.fail_closed(nullptr);
+  if (!b || !sized || !tsig_counts_ok(1, m) || !shares || !o.complete()) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::TdsaShare, dsa_keyset, m, pbytes, qbytes);
+  r.th_k = m; r.th_nbytes = pbytes; r.th_qbytes = qbytes; r.th_a = shares; r.ks_key = group_idx;
+  return tsig_share_submit(b, r, o);
+}
+int bftkv_gpu_batcher_tecdsa_share(bftkv_gpu_batcher* b, uint32_t m, const uint8_t* shares, const uint8_t* curve, uint32_t bit_size, uint8_t* ri_out,
+                                   uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out) {
+  const bool sized = bit_size != 0 && bit_size <= 521;
+  const uint32_t f = (bit_size + 7) / 8;
+  const TsigOut o{ri_out, vi_out, ki_out, ci_out, status_out, 1, sized ? 1 + 2 * (size_t)f : 0, sized ? f : 0u, false};
+  (void)o.fail_closed(nullptr);
+  if (!b || !sized || !curve || !tsig_counts_ok(1, m) || !shares || !o.complete()) return BFTKV_E_INVALID;
+  if (ec_curve_id(curve, bit_size) < 0) return BFTKV_E_UNSUPPORTED;       // for this caller alone
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::TecdsaShare, bftkv_gpu_batcher::NO_QUORUM, m, bit_size);
+  r.th_k = m; r.th_nbytes = f; r.th_qbytes = bit_size; r.th_a = shares; r.th_mod = curve;
+  return tsig_share_submit(b, r, o);
 }
 
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]) {

@@ -40,6 +40,7 @@
 #include "rsa_verify_kernels.hip"
 #include "tpa_kernels.hip"
 #include "rsa_psign_kernels.hip"
+#include "tsig_share_kernels.hip"
 
 using namespace bftkv;
 
@@ -135,9 +136,10 @@ struct DsaKeySet {
   DevBuf tab;                              // [n_groups + n_keys][windows][2^w - 1][76], fully reduced Montgomery entries (R = 2^2128)
   ModRows modp, modq;                      // every p and q
   DevBuf q_be, key_group;                  // [n_groups][qbytes] bytes; [n_keys] clamped group indices
+  DevBuf qc;                               // [n_groups] TsigMod<8>: every q in the eight-word form of tsig_share.h (bftkv_gpu_tdsa_share)
   uint64_t table_bytes() const { return (uint64_t)(n_groups + n_keys) * windows * ((1u << w) - 1u) * MONT_N * 4; }
   size_t sig_bytes() const { return 2 * (size_t)qbytes; }
-  void release() { tab.release(); q_be.release(); key_group.release(); modp.release(); modq.release(); }
+  void release() { tab.release(); q_be.release(); key_group.release(); qc.release(); modp.release(); modq.release(); }
 };
 
 // A resident RSA key set (rsa_verify_capi.inc): the keys' Montgomery rows in both forms of k_rsav_verify.  An even modulus has
@@ -2451,6 +2453,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "rsa_verify_capi.inc"
 #include "tpa_capi.inc"
 #include "rsa_psign_capi.inc"
+#include "tsig_share_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

@@ -33,6 +33,11 @@ int dsa_keyset_create_impl(bftkv_gpu_ctx* c, uint32_t n_keys, const uint8_t* key
       return KeySets<DsaKeySet>::nomem(c);
     HIPCHK(c, hipMemcpyAsync(ks.q_be.p, q, (size_t)n_groups * qbytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(ks.key_group.p, hb.key_group.data(), (size_t)n_keys * 4, hipMemcpyHostToDevice, c->stream));
+    // every q once more in the word form of the share answers (bftkv_gpu_tdsa_share): no verification reads it
+    std::vector<TsigMod<8>> qc(n_groups);
+    for (uint32_t i = 0; i < n_groups; ++i) tsig_mod_setup<8>(qc[i], q + (size_t)i * qbytes, qbytes);
+    if (ks.qc.ensure_exact(qc.size() * sizeof(TsigMod<8>)) != hipSuccess) return KeySets<DsaKeySet>::nomem(c);
+    HIPCHK(c, hipMemcpyAsync(ks.qc.p, qc.data(), qc.size() * sizeof(TsigMod<8>), hipMemcpyHostToDevice, c->stream));
     // the bases as one array of limbs (scratch of this call)
     const uint32_t n_bases = n_groups + n_keys;
     uint32_t* d_bases;

@@ -408,6 +408,69 @@ EC_HD void fb_mul(Jac<L>& R, const uint32_t* tab, uint32_t w, uint32_t nwin, con
   R = acc;
 }
 
+// One step of fb_mul_fixed: P <- P where `keep`, (qx, qy, 1) where `first`, P + (qx, qy) otherwise (the masks are all ones or zero,
+// at most one of them set).  The sum is pt_add_affine's GENERAL case alone, whatever P is -- no test for infinity, equal or opposite
+// operands -- and each coordinate is settled by a word-wise select as soon as the formulas have no more use for the old one, so the
+// step holds one point, not two.  Where the masks discard the sum, its words are arithmetic on whatever P held (zeroes before the
+// first digit): defined, and unused.
+template <int L>
+EC_HD void pt_add_affine_fixed(Jac<L>& P, const uint32_t* qx, const uint32_t* qy, uint32_t keep, uint32_t first, const Curve<L>& C) {
+  const uint32_t take = ~(keep | first);
+  uint32_t h[L], rr[L], t[L], v[L];
+  fp_sqr<L>(t, P.z, C);
+  fp_mul<L>(h, qx, t, C);
+  fp_sub<L>(h, h, P.x, C);                              // H = X2 Z1^2 - X1
+  fp_mul<L>(t, t, P.z, C);
+  fp_mul<L>(rr, qy, t, C);
+  fp_sub<L>(rr, rr, P.y, C);                            // r = Y2 Z1^3 - Y1
+  fp_mul<L>(t, P.z, h, C);                              // Z3 = Z1 H
+#pragma unroll
+  for (int j = 0; j < L; ++j) P.z[j] = (P.z[j] & keep) | (t[j] & take) | (C.one[j] & first);
+  fp_sqr<L>(t, h, C);                                   // H^2
+  fp_mul<L>(v, P.x, t, C);                              // V = X1 H^2
+  fp_mul<L>(h, h, t, C);                                // H^3
+  fp_sqr<L>(t, rr, C);
+  fp_sub<L>(t, t, h, C);
+  fp_sub<L>(t, t, v, C);
+  fp_sub<L>(t, t, v, C);                                // X3 = r^2 - H^3 - 2 V
+  fp_mul<L>(h, P.y, h, C);                              // Y1 H^3
+  fp_sub<L>(v, v, t, C);                                // V - X3
+#pragma unroll
+  for (int j = 0; j < L; ++j) P.x[j] = (P.x[j] & keep) | (t[j] & take) | (qx[j] & first);
+  fp_mul<L>(t, rr, v, C);
+  fp_sub<L>(t, t, h, C);                                // Y3 = r (V - X3) - Y1 H^3
+#pragma unroll
+  for (int j = 0; j < L; ++j) P.y[j] = (P.y[j] & keep) | (t[j] & take) | (qy[j] & first);
+}
+
+// k B for k < N from the table of B, with a sequence of operations that does not depend on k (a secret share's multiple of G,
+// dsaContext.Sign): EVERY window loads an entry -- its digit's, or digit 1's where the digit is 0 -- and runs the general mixed
+// addition; the digit decides only the entry's address and the masks of the select.  The general formulas suffice for k < N: before
+// window i the accumulator is t B with t < 2^(w i), the entry is d 2^(w i) B with d >= 1, so t < d 2^(w i) <= k < N and the two are
+// never equal, and they are opposite only if t + d 2^(w i), a prefix of k and at most k, were N.  k = 0 keeps
+// the zeroes the accumulator starts with: infinity.  fb_mul stays the route of public scalars (it skips zero digits).
+template <int L>
+EC_HD void fb_mul_fixed(Jac<L>& R, const uint32_t* tab, uint32_t w, uint32_t nwin, const uint32_t* k, const Curve<L>& C) {
+  uint32_t kw[L], qx[L], qy[L];
+  fe_copy<L>(kw, k);
+  Jac<L> acc;
+  pt_set_inf<L>(acc);
+  const uint32_t mask = (1u << w) - 1u;
+  uint32_t started = 0;                                 // all ones from the first non-zero digit on
+  for (uint32_t i = 0; i < nwin; ++i) {
+    const uint32_t d = kw[0] & mask;
+#pragma unroll
+    for (int j = 0; j < L; ++j) kw[j] = (kw[j] >> w) | (j + 1 < L ? kw[j + 1] << (32u - w) : 0u);
+    const uint32_t nz = 0u - (uint32_t)(d != 0);
+    const uint32_t* e = tab + (((size_t)i * 2 * L) << w) + (d | (1u & ~nz));
+#pragma unroll
+    for (int j = 0; j < L; ++j) { qx[j] = e[(size_t)j << w]; qy[j] = e[(size_t)(L + j) << w]; }
+    pt_add_affine_fixed<L>(acc, qx, qy, ~nz, nz & ~started, C);
+    started |= nz;
+  }
+  R = acc;
+}
+
 // ---- constants, on the host (once per curve and context) -------------------------------------------------------------
 EC_HD uint32_t neg_inv32(uint32_t m0) {      // -m0^-1 mod 2^32 (m0 odd), Newton
   uint32_t x = m0;

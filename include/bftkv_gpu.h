@@ -450,6 +450,18 @@ int bftkv_gpu_batcher_tpa_bi(bftkv_gpu_batcher* b, const uint8_t* v, const uint8
 int bftkv_gpu_batcher_rsa_partial_sign(bftkv_gpu_batcher* b, const uint8_t* t, uint32_t t_len, const uint8_t* mod, uint32_t nbytes, uint32_t n_frags,
                                        const uint8_t* exps, uint32_t exp_len, const uint32_t* exp_used, const uint8_t* sign, uint8_t* out,
                                        uint8_t* status_out);
+/* ONE sign request of a threshold DSA / ECDSA server with its m shares (bftkv_gpu_tdsa_share / bftkv_gpu_tecdsa_share below;
+ * dsaContext.Sign, phase 2).  shares is [m][4][qbytes] (DSA) or [m][4][f] (ECDSA, f = (bit_size + 7) / 8): k, a, b, c of every share.
+ * DSA: dsa_keyset names a resident DSA key set, group_idx one of its groups (clamped); pbytes and qbytes are the set's widths as
+ * bftkv_gpu_dsa_keyset_info reports them (they size the outputs; a request whose widths are not the set's is refused).  Outputs: ri_out
+ * [pbytes] or [1 + 2 f], vi_out, ki_out, ci_out [qbytes] or [f], one status byte.  Callers are grouped by (set or curve, m).  What the
+ * batched entry refuses for the whole call returns BFTKV_E_INVALID -- an unrecognised curve BFTKV_E_UNSUPPORTED -- for that caller
+ * alone, before it joins a batch.  Whenever the return code is not 0, the status is BFTKV_TH_FAILED and every output byte 0.  The shares
+ * are SECRETS (bftkv_gpu_tdsa_share).  The last phase (bftkv_gpu_tsig_partial_s) has no entry here: it is three products mod q. */
+int bftkv_gpu_batcher_tdsa_share(bftkv_gpu_batcher* b, int dsa_keyset, uint32_t group_idx, uint32_t m, const uint8_t* shares, uint32_t pbytes,
+                                 uint32_t qbytes, uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out);
+int bftkv_gpu_batcher_tecdsa_share(bftkv_gpu_batcher* b, uint32_t m, const uint8_t* shares, const uint8_t* curve, uint32_t bit_size,
+                                   uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out);
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]);
 /* where the callers' time went, nanoseconds summed over all calls so far: [0] hashing their payloads, [1] leaders waiting
  * for a lane, [2] leaders assembling batches, [3] leaders inside device calls, of which [4] enqueueing and [5] waiting
@@ -840,6 +852,44 @@ int bftkv_gpu_rsa_partial_sign(bftkv_gpu_ctx* ctx, uint32_t n_reqs, const uint8_
                                const uint32_t* mod_idx, uint32_t n_mods, const uint8_t* mods, uint32_t nbytes, uint32_t n_frags,
                                const uint32_t* frag_req, const uint8_t* exps, uint32_t exp_len, const uint32_t* exp_used, const uint8_t* sign,
                                uint8_t* out, uint8_t* status_out);
+
+/* ---- threshold DSA / ECDSA signing, the server's side (docs/parity.md "Threshold DSA / ECDSA signing (dsaContext.Sign)") ---------
+ * dsaContext.Sign (crypto/threshold/dsa/dsa_core.go:91-163) from a request's decrypted shares to the fields of its answer, in one
+ * device pass.  Phase 2 (:126-141, with decrypt's fold :235-238): the caller holds m >= 1 shares (k_j, a_j, b_j, c_j) of one x, as
+ * non-negative integers of the row width, any value of it.  Per request
+ *   ki = sum k_j mod q    ai = sum a_j mod q    bi = sum b_j mod q    ci = sum c_j mod q
+ *   ri = g^ai mod p (DSA, pbytes wide) or Marshal(ai G) = 04 | x | y (ECDSA; 04 | 0 .. 0 for ai = 0)
+ *   vi = ((ki ai mod q) + bi) mod q
+ * The server sends x, ri, vi and keeps (ki, ci).  Every status is BFTKV_TH_OK: no input of the row width is refused or fenced.
+ *   bftkv_gpu_tdsa_share: the group (p, q, g) is group_idx[r] (NULL: group 0; an index past the set's groups is clamped) of a resident
+ *       DSA key set, whose widths are the call's: shares [n_reqs][m][4][qbytes], ri_out [n_reqs][pbytes], vi_out, ki_out, ci_out
+ *       [n_reqs][qbytes].  ri comes from the set's window table of g: one product per window of the set, whatever ai.
+ *   bftkv_gpu_tecdsa_share: curve and bit_size as for bftkv_gpu_ecdsa_calculate_r (an unrecognised group: BFTKV_E_UNSUPPORTED), q is
+ *       the curve's N, f = (bit_size + 7) / 8: shares [n_reqs][m][4][f], ri_out [n_reqs][1 + 2 f], vi_out, ki_out, ci_out [n_reqs][f].
+ *       ri comes from the context's table of G: one mixed addition per window, whatever ai.
+ *   The _dev forms take every per-request array resident in HBM and leave the results there, asynchronous on the context's stream.
+ * Phase 3 (:150-155), bftkv_gpu_tsig_partial_s, one entry for both schemes since only q differs:
+ *   si = ((((r y mod q) + m) mod q) k mod q + c) mod q
+ * m_in, r, y, k, c and si_out are [n_reqs][nbytes], 1 <= nbytes <= 66, any value of the width; mod_idx [n_reqs] into q
+ * [n_mods][nbytes] (NULL: modulus 0; an index past the table is clamped to its last row).
+ * The shares, ki, ci and y are SECRETS: the sequence of operations does not depend on them (the address of a table row does depend on
+ * a digit of ai).  A deployment decides whether they may leave the host.  A share, m, r or y longer than its row is not submitted: the
+ * caller keeps the reference path.
+ * BFTKV_E_INVALID: a NULL context, array or a bad key set handle, n_reqs or n_mods 0, m 0 or > 1024, n_reqs * m > 2^22, nbytes 0 or >
+ * 66.  BFTKV_E_UNSUPPORTED: an even q in bftkv_gpu_tsig_partial_s's table (a key set holds none).  Whenever the return code is not 0,
+ * every status is BFTKV_TH_FAILED and every output byte 0 (under a bad key set handle the widths of the outputs are unknown: the
+ * statuses fail and the outputs are left as they were). */
+int bftkv_gpu_tdsa_share(bftkv_gpu_ctx* ctx, int dsa_keyset, uint32_t n_reqs, const uint32_t* group_idx, uint32_t m, const uint8_t* shares,
+                         uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out);
+int bftkv_gpu_tdsa_share_dev(bftkv_gpu_ctx* ctx, int dsa_keyset, uint32_t n_reqs, const uint32_t* group_idx, uint32_t m, const uint8_t* shares,
+                             uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out);
+int bftkv_gpu_tecdsa_share(bftkv_gpu_ctx* ctx, uint32_t n_reqs, uint32_t m, const uint8_t* shares, const uint8_t* curve, uint32_t bit_size,
+                           uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out);
+int bftkv_gpu_tecdsa_share_dev(bftkv_gpu_ctx* ctx, uint32_t n_reqs, uint32_t m, const uint8_t* shares, const uint8_t* curve, uint32_t bit_size,
+                               uint8_t* ri_out, uint8_t* vi_out, uint8_t* ki_out, uint8_t* ci_out, uint8_t* status_out);
+int bftkv_gpu_tsig_partial_s(bftkv_gpu_ctx* ctx, uint32_t n_reqs, const uint8_t* m_in, const uint8_t* r, const uint8_t* y, const uint8_t* k,
+                             const uint8_t* c, uint32_t nbytes, const uint32_t* mod_idx, uint32_t n_mods, const uint8_t* q, uint8_t* si_out,
+                             uint8_t* status_out);
 
 /* ---- timing of the last *_dev verify call (HIP events on the context's stream) ---------------- */
 /* ms[0] whole call, ms[1] walk+parse, ms[2] hash stream (midstates+digests, overlaps the modexp),

@@ -60,6 +60,8 @@ EXPORTS = [
     "bftkv_gpu_rsa_partial_sign", "bftkv_gpu_batcher_rsa_partial_sign",
     "bftkv_gpu_tdsa_share", "bftkv_gpu_tdsa_share_dev", "bftkv_gpu_tecdsa_share", "bftkv_gpu_tecdsa_share_dev", "bftkv_gpu_tsig_partial_s",
     "bftkv_gpu_batcher_tdsa_share", "bftkv_gpu_batcher_tecdsa_share",
+    "bftkv_gpu_rsa_signer_create", "bftkv_gpu_rsa_signer_destroy", "bftkv_gpu_rsa_signer_info", "bftkv_gpu_rsa_sign_keyset",
+    "bftkv_gpu_rsa_sign_keyset_dev", "bftkv_gpu_selftest_rsa_crt", "bftkv_gpu_batcher_rsa_sign_keyset",
 ]
 
 _lib = None
@@ -193,6 +195,13 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_tsig_partial_s.argtypes = [vp, u32, u8p, u8p, u8p, u8p, u8p, u32, vp, u32, u8p, u8p, u8p]
     lib.bftkv_gpu_batcher_tdsa_share.argtypes = [vp, C.c_int, u32, u32, u8p, u32, u32, u8p, u8p, u8p, u8p, u8p]
     lib.bftkv_gpu_batcher_tecdsa_share.argtypes = [vp, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p, u8p]
+    lib.bftkv_gpu_rsa_signer_create.argtypes = [vp, u32, u8p, vp, u32, u8p, u8p, u8p, u8p, u8p, u32, C.POINTER(C.c_int)]
+    lib.bftkv_gpu_rsa_signer_destroy.argtypes = [vp, C.c_int]
+    lib.bftkv_gpu_rsa_signer_info.argtypes = [vp, C.c_int] + [C.POINTER(u32)] * 4
+    lib.bftkv_gpu_rsa_sign_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u32, vp, u8p, u8p]
+    lib.bftkv_gpu_rsa_sign_keyset_dev.argtypes = [vp, C.c_int, u32, vp, u32, u32, vp, vp, vp]
+    lib.bftkv_gpu_selftest_rsa_crt.argtypes = [vp, C.c_int, u32, u8p, vp, u8p, u8p]
+    lib.bftkv_gpu_batcher_rsa_sign_keyset.argtypes = [vp, C.c_int, u32, u8p, u32, u32, u8p, u8p]
     for name in EXPORTS:
         if name not in ("bftkv_gpu_destroy", "bftkv_gpu_last_error", "bftkv_gpu_error_string", "bftkv_gpu_stream",
                         "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_destroy"):
@@ -805,6 +814,61 @@ class Context:
         return self._verdicts("rsa_verify_keyset", "digests of one length, sigs of the set's nbytes", digests, sigs, self.rsa_keyset_info(keyset)["nbytes"], key_idx,
                               lambda n, dg, dlen, sg, ki, valid, st: self.lib.bftkv_gpu_rsa_verify_keyset(self.h, keyset, n, dg, hash_id, dlen, sg, ki, valid, st))
 
+    # ---- raw RSA signing under resident private key sets (rsa.SignPKCS1v15)
+    def rsa_signer_create(self, keys, nbytes=None, pbytes=None) -> int:
+        """Register private keys, dicts of ints {n, e, p, q, dp, dq, qinv}: their rows stay on the device.  A key with an even n, or
+        with p or q even or below 3, does not refuse the set (rsa_signer_info counts it; its signatures are fenced).  nbytes and pbytes
+        default to the widest modulus and the widest of the private parts."""
+        if nbytes is None:
+            nbytes = max(1, max((int(k["n"]).bit_length() + 7) // 8 for k in keys))
+        if pbytes is None:
+            pbytes = max(1, max((int(k[f]).bit_length() + 7) // 8 for k in keys for f in ("p", "q", "dp", "dq", "qinv")))
+        kn = _ints_to_be([k["n"] for k in keys], nbytes)
+        ke = np.ascontiguousarray([k["e"] for k in keys], dtype=np.uint32)
+        parts = [_ints_to_be([k[f] for k in keys], pbytes) for f in ("p", "q", "dp", "dq", "qinv")]
+        h = C.c_int(-1)
+        self._check(self.lib.bftkv_gpu_rsa_signer_create(self.h, len(keys), _ptr(kn), _ptr(ke), nbytes, *[_ptr(a) for a in parts], pbytes, C.byref(h)),
+                    "rsa_signer_create")
+        return h.value
+
+    def rsa_signer_destroy(self, signer: int):
+        self._check(self.lib.bftkv_gpu_rsa_signer_destroy(self.h, signer), "rsa_signer_destroy")
+
+    def rsa_signer_info(self, signer: int):
+        """-> {n_keys, n_refused, nbytes, pbytes}"""
+        v = [C.c_uint32() for _ in range(4)]
+        self._check(self.lib.bftkv_gpu_rsa_signer_info(self.h, signer, *[C.byref(x) for x in v]), "rsa_signer_info")
+        return dict(zip(("n_keys", "n_refused", "nbytes", "pbytes"), (x.value for x in v)))
+
+    def rsa_sign_keyset(self, signer: int, digests, hash_id: int, key_idx=None):
+        """rsa.SignPKCS1v15 on raw digests under the keys of a signer set: digests [n_ops] bytes of ONE length (the size of hash_id's
+        hash; 1..64 for hash_id 0), key_idx [n_ops] into the set or None (key 0) -> (sigs [n_ops, nbytes], status [n_ops]), uint8."""
+        n = len(digests)
+        dlen = len(digests[0]) if n else 0
+        if any(len(d) != dlen for d in digests):
+            raise ValueError("rsa_sign_keyset: digests of one length")
+        dg = np.frombuffer(b"".join(bytes(d) for d in digests), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        assert ki is None or len(ki) == n
+        nbytes = self.rsa_signer_info(signer)["nbytes"]
+        sig, st = np.zeros((n, nbytes), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_rsa_sign_keyset(self.h, signer, n, _ptr(dg), hash_id, dlen, None if ki is None else ki.ctypes.data, _ptr(sig),
+                                                       _ptr(st)), "rsa_sign_keyset")
+        return sig, st
+
+    def selftest_rsa_crt(self, signer: int, values, key_idx=None):
+        """The chains and the recombination on values [n_ops] ints below 2^(8 nbytes), without padding and without the check
+        -> (out [n_ops, nbytes], status [n_ops])."""
+        nbytes = self.rsa_signer_info(signer)["nbytes"]
+        n = len(values)
+        cv = _ints_to_be(list(values), nbytes) if n else np.zeros((1, nbytes), dtype=np.uint8)
+        ki = None if key_idx is None else np.ascontiguousarray(key_idx, dtype=np.uint32)
+        assert ki is None or len(ki) == n
+        out, st = np.zeros((n, nbytes), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.bftkv_gpu_selftest_rsa_crt(self.h, signer, n, _ptr(cv), None if ki is None else ki.ctypes.data, _ptr(out), _ptr(st)),
+                    "selftest_rsa_crt")
+        return out, st
+
     # ---- threshold password authentication (crypto/auth): rows of uint8, big-endian
     def tpa_yi(self, x, y, mods, mod_idx=None):
         """makeYi: yi[i] = x[i] ^ y[i] mod mods[mod_idx[i]].  x [n, nbytes], y [n, exp_len], mods [m, nbytes], mod_idx [n] or None
@@ -1143,6 +1207,14 @@ class Batcher:
         vi, ki, ci = (np.full(f, 0xAA, dtype=np.uint8) for _ in range(3))
         rc = self.lib.bftkv_gpu_batcher_tecdsa_share(self.h, m, _ptr(sh), _ptr(cb), bits, _ptr(ri), _ptr(vi), _ptr(ki), _ptr(ci), _ptr(st))
         return rc, int(st[0]), ri.tobytes(), vi.tobytes(), ki.tobytes(), ci.tobytes()
+
+    def rsa_sign_keyset(self, signer: int, key: int, digest: bytes, hash_id: int):
+        """rsa.SignPKCS1v15 for one digest under key `key` of a resident signer set -> (rc, status, signature bytes of the set's nbytes)."""
+        nbytes = self.ctx.rsa_signer_info(signer)["nbytes"]
+        dg = np.frombuffer(bytes(digest), dtype=np.uint8).copy() if digest else np.zeros(1, dtype=np.uint8)
+        sig, st = np.full(nbytes, 0xAA, dtype=np.uint8), np.zeros(1, dtype=np.uint8)
+        rc = self.lib.bftkv_gpu_batcher_rsa_sign_keyset(self.h, signer, key, _ptr(dg), len(digest), hash_id, _ptr(sig), _ptr(st))
+        return rc, int(st[0]), sig.tobytes()
 
     def stats(self):
         st = (C.c_uint64 * 4)()

@@ -281,7 +281,8 @@ struct bftkv_gpu_batcher {
     EcdsaCalculateR, EcdsaVerify, EcdsaVerifyKeyset, DsaVerify, DsaVerifyKeyset, RsaVerify, RsaVerifyKeyset,
     TpaYi, TpaBi,                                              // ONE password-authentication answer of a server: makeYi, makeBi (crypto/auth)
     RsaPartialSign,                                            // ONE threshold-RSA sign request of a server with all its fragments: rsaContext.Sign
-    TdsaShare, TecdsaShare                                     // ONE threshold DSA / ECDSA sign request of a server with its m shares: dsaContext.Sign, phase 2
+    TdsaShare, TecdsaShare,                                    // ONE threshold DSA / ECDSA sign request of a server with its m shares: dsaContext.Sign, phase 2
+    RsaSignKeyset                                              // ONE raw RSA signature under a resident signer set: rsa.SignPKCS1v15
   };
   static bool hashed_by_caller(Kind k) { return k == Kind::Collective || k == Kind::Signature; }      // a SHA-256 midstate of tbs goes to the device, not tbs
   static bool threshold_style(Kind k) { return k >= Kind::ModmulProduct; }      // th_* fields in, a BFTKV_TH_* status byte and th_out out
@@ -308,6 +309,7 @@ struct bftkv_gpu_batcher {
   //   RsaPartialSign            -       frags nbytes     exp bytes  -      T               magnitudes  N       -              -           T len   frags x nbytes
   //   TdsaShare                 set     m     pb         qb         -      m shares (4 qb) -           -       -              -           group   1 x pb
   //   TecdsaShare               -       m     f          bit size   -      m shares (4 f)  -           curve   -              -           -       1 x (1 + 2 f)
+  //   RsaSignKeyset             set     dlen  -          hash id    -      digest          -           -       -              -           key     nbytes of the set
   // (TpaBi: th_k is the salt's length; its keys and MAC, 32 bytes each, go to tpa_keys and tpa_mac.)
   // (RsaPartialSign: th_k is the request's fragment count; ps_used and ps_sign are its widths and sign bytes, ps_status its status bytes.)
   // (TdsaShare, TecdsaShare: th_out is ri; vi, ki and ci go to ts_vi, ts_ki and ts_ci, qb or f bytes each.  TdsaShare's pb and qb are the
@@ -804,6 +806,40 @@ struct bftkv_gpu_batcher {
     }
   }
 
+  // RsaSignKeyset: a group's callers share (set, hash id, dlen).  The lane holds its hold on the root's tables from the look at the set,
+  // which tells the width of a signature, to the end of the device call (run_verify_keyset).  Whatever fails, a caller whose set was
+  // found gets a row of zeroes.
+  void run_rsa_sign(Lane& lane, std::vector<Req*>& g, uint64_t& device_calls) {
+    const Req& r0 = *g[0];
+    const uint32_t n = (uint32_t)g.size(), dlen = r0.th_k, hash_id = r0.th_qbytes;
+    std::vector<uint8_t> sig, st((size_t)n + 8, BFTKV_TH_FAILED);
+    size_t sw = 0;
+    int rc;
+    {
+      ctx_lock lk(lane.ctx->mu);
+      KtRead kr(lane.ctx);
+      const RsaSignerSet* ks = kr.rc ? nullptr : KeySets<RsaSignerSet>::find(lane.ctx, r0.quorum);
+      sw = ks ? ks->sig_bytes() : 0;
+      if (kr.rc) rc = kr.rc;
+      else if (!sw) rc = BFTKV_E_INVALID;
+      else {
+        const std::vector<uint8_t> dg = gather(g, &Req::th_a, dlen);
+        std::vector<uint32_t> idx(n);
+        for (uint32_t i = 0; i < n; ++i) idx[i] = g[i]->ks_key;
+        sig.assign((size_t)n * sw, 0);
+        rc = rsa_sign_impl(lane.ctx, r0.quorum, n, dg.data(), hash_id, dlen, nullptr, idx.data(), sig.data(), st.data(), false, false);
+        if (rc) std::fill(sig.begin(), sig.end(), 0);
+        ++device_calls;
+      }
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+      Req* r = g[i];
+      r->rc = rc;
+      r->err = rc ? Req::failing(r->kind) : st[i];
+      if (sw) memcpy(r->th_out, &sig[i * sw], sw);
+    }
+  }
+
   // group by (kind, quorum / certificate use, threshold shape): one device call per group
   uint64_t process(Lane& lane, std::vector<Req*>& batch) {
     uint64_t calls = 0;     // device calls made for this batch
@@ -842,6 +878,7 @@ struct bftkv_gpu_batcher {
         case Kind::TpaYi: case Kind::TpaBi: run_tpa(lane, g, calls); break;
         case Kind::RsaPartialSign: run_psign(lane, g, calls); break;
         case Kind::TdsaShare: case Kind::TecdsaShare: run_tsig_share(lane, g, calls); break;
+        case Kind::RsaSignKeyset: run_rsa_sign(lane, g, calls); break;
       }
     }
     return calls;
@@ -1290,6 +1327,17 @@ int bftkv_gpu_batcher_tecdsa_share(bftkv_gpu_batcher* b, uint32_t m, const uint8
   bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::TecdsaShare, bftkv_gpu_batcher::NO_QUORUM, m, bit_size);
   r.th_k = m; r.th_nbytes = f; r.th_qbytes = bit_size; r.th_a = shares; r.th_mod = curve;
   return tsig_share_submit(b, r, o);
+}
+
+// ONE raw RSA signature under key `key` of a resident signer set.  A caller whose (hash id, dlen) the batched entry would refuse for the
+// WHOLE call is refused here alone, before it joins a batch.
+int bftkv_gpu_batcher_rsa_sign_keyset(bftkv_gpu_batcher* b, int set, uint32_t key, const uint8_t* digest, uint32_t dlen, uint32_t hash_id,
+                                      uint8_t* sig_out, uint8_t* status_out) {
+  if (status_out) *status_out = BFTKV_TH_FAILED;
+  if (!b || !status_out || !sig_out || !digest || !rsav_shape_ok(hash_id, dlen, 1)) return BFTKV_E_INVALID;
+  bftkv_gpu_batcher::Req r = threshold_req(BatcherKind::RsaSignKeyset, set, dlen, hash_id);
+  r.th_k = dlen; r.th_qbytes = hash_id; r.th_a = digest; r.th_out = sig_out; r.ks_key = key;
+  return threshold_submit(b, r, status_out);
 }
 
 int bftkv_gpu_batcher_stats(bftkv_gpu_batcher* b, uint64_t stats[4]) {

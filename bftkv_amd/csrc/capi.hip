@@ -41,6 +41,7 @@
 #include "tpa_kernels.hip"
 #include "rsa_psign_kernels.hip"
 #include "tsig_share_kernels.hip"
+#include "rsa_sign_kernels.hip"
 
 using namespace bftkv;
 
@@ -154,6 +155,20 @@ struct RsaKeySet {
   void release() { n29.release(); r2_29.release(); n80.release(); r2_80.release(); meta.release(); }
 };
 
+// A resident RSA private key set (rsa_sign_capi.inc): per key the rows of p and q in the 10 x 4 form (R = 2^1120), dp and dq as bytes,
+// qinv R mod p, and the verifier's rows of (n, e) for the check.  A refused key (n even; p or q even or below 3) has zero rows.
+struct RsaSignerSet {
+  static constexpr const char* kind = "RSA signer";
+  bool live = false;
+  uint32_t n_keys = 0, n_refused = 0, nbytes = 0, pbytes = 0;
+  DevBuf mod, r2, r3, n0;                  // [n_keys][2][40] p | q, R^2 and R^3 mod each; [n_keys][2] -p^-1, -q^-1 mod 2^28        SECRET
+  DevBuf d, qinv_r;                        // [n_keys][2][pbytes] dp | dq; [n_keys][40] qinv R mod p                              SECRET
+  DevBuf refused;                          // [n_keys] bytes
+  DevBuf n29, r2_29, meta;                 // the rows of an RsaKeySet's 18 x 4 form
+  size_t sig_bytes() const { return nbytes; }
+  void release();                          // overwrites the secret rows before it frees them
+};
+
 }  // namespace
 
 using ctx_lock = std::lock_guard<std::recursive_mutex>;
@@ -209,8 +224,8 @@ struct bftkv_gpu_ctx {
   KeyTableDev kt{};
 
   std::vector<QuorumHost> quorums;
-  // root: the handles of bftkv_gpu_{ecdsa,dsa,rsa}_keyset_create, a space per kind; forks read them under KtRead, without a copy (KeySets)
-  std::tuple<std::vector<EcKeySet>, std::vector<DsaKeySet>, std::vector<RsaKeySet>> keysets;
+  // root: the handles of bftkv_gpu_{ecdsa,dsa,rsa}_keyset_create and bftkv_gpu_rsa_signer_create, a space per kind; forks read them under KtRead, without a copy (KeySets)
+  std::tuple<std::vector<EcKeySet>, std::vector<DsaKeySet>, std::vector<RsaKeySet>, std::vector<RsaSignerSet>> keysets;
 
   // per-call arena
   DevBuf txt_mid32, txt_mid64, txt_tail, txt_len;     // text-mode hashing state (TextDev)
@@ -2454,6 +2469,7 @@ extern "C" int bftkv_host_cert_fingerprint(const uint8_t* cert, uint64_t len, ui
 #include "tpa_capi.inc"
 #include "rsa_psign_capi.inc"
 #include "tsig_share_capi.inc"
+#include "rsa_sign_capi.inc"
 #include "message_capi.inc"
 #include "batcher_capi.inc"
 #include "host_capi.inc"

@@ -428,6 +428,15 @@ int bftkv_gpu_batcher_rsa_verify(bftkv_gpu_batcher* b, const uint8_t* digest, ui
  * RUNS: the caller must not destroy a set while calls that name it are in flight. */
 int bftkv_gpu_batcher_rsa_verify_keyset(bftkv_gpu_batcher* b, int keyset, uint32_t key, const uint8_t* digest, uint32_t hash_id, uint32_t dlen,
                                         const uint8_t* sig, uint8_t* valid_out, uint8_t* status_out);
+/* ONE signature under key `key` of a resident RSA signer set (bftkv_gpu_rsa_signer_create on the batcher's context; the rules:
+ * bftkv_gpu_rsa_sign_keyset below): one goroutine's Signature.Sign or CollectiveSignature.Sign joins a device batch.  sig_out [nbytes
+ * of the set]; an index past the set is clamped to its last key.  Callers are grouped by (set, hash_id, dlen).  A caller whose (hash_id,
+ * dlen) the batched entry would refuse for the WHOLE call is refused here alone, before it joins a batch; an unknown or destroyed
+ * handle returns BFTKV_E_INVALID for its own group alone.  Results start as failures: whenever the return code is not 0, *status_out
+ * is BFTKV_TH_FAILED, and every byte of sig_out is 0 whenever the lane found the set (which alone tells the row's width).  The lane
+ * writes nbytes of `sig_out` for the set the handle names when the request RUNS: no destroy while calls that name it are in flight. */
+int bftkv_gpu_batcher_rsa_sign_keyset(bftkv_gpu_batcher* b, int set, uint32_t key, const uint8_t* digest, uint32_t dlen, uint32_t hash_id,
+                                      uint8_t* sig_out, uint8_t* status_out);
 /* ONE answer of a server in the threshold password authentication (bftkv_gpu_tpa_yi / bftkv_gpu_tpa_bi below; makeYi and makeBi of
  * crypto/auth/auth.go, driven by Server.authenticate, protocol/server.go:405-448).  x, v, mod and the outputs are [nbytes], y and
  * bexp [exp_len], big-endian; xi points at the request's xi_len bytes (0 .. nbytes; may be NULL when xi_len is 0) and salt at
@@ -786,6 +795,55 @@ int bftkv_gpu_rsa_verify_keyset(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, 
 /* same with the per-signature arrays resident in HBM: nothing is read from host memory, the call never waits */
 int bftkv_gpu_rsa_verify_keyset_dev(bftkv_gpu_ctx* ctx, int keyset, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen,
                                     const uint8_t* sigs, const uint32_t* key_idx, uint8_t* valid_out, uint8_t* status_out);
+
+/* ---- raw RSA PKCS#1 v1.5 signing under resident private key sets (docs/parity.md "RSA signing (rsa.SignPKCS1v15)") -------------
+ * Go 1.13's rsa.SignPKCS1v15(rand, priv, hash, hashed) on raw inputs: digest in, signature bytes out -- what openpgp.DetachSign ends in
+ * for Signature.Sign (protocol/client.go:131, :445) and CollectiveSignature.Sign (protocol/server.go:264, :425).  Hashing tbs | suffix
+ * and assembling the signature packet stay with the caller.  Keys of at most 2048 bits with two primes of at most 1024 bits each.
+ * Per signature, with k = ceil(bits(n) / 8) and tLen = prefix length + dlen (hash ids and prefixes: bftkv_gpu_rsa_verify), in this order:
+ *   k < tLen + 11 (n = 0 and n = 1 included)      BFTKV_TH_INVALID_INPUT, zeroes   (Go: ErrMessageTooLong), whatever the key's state
+ *   the key was refused at registration           BFTKV_TH_FENCED, zeroes
+ *   s^e mod n != em, or s does not fit nbytes     BFTKV_TH_CHECK_FAILED, zeroes    (Go: "rsa: internal error"; crypto.ErrSigningFailed)
+ *   otherwise                                     BFTKV_TH_OK, s big-endian, left-padded to nbytes
+ * with em = 00 01 FF .. FF 00 | prefix | digest of k bytes, m1 = em^dp mod p, m2 = em^dq mod q, h = (m1 - m2) qinv mod p and
+ * s = m2 + h q (rsa.decrypt's precomputed branch; blinding changes no output byte).  dp, dq and qinv are taken as given: a key whose
+ * parts do not agree is not detected at registration -- its signatures fail the check, so that a corrupted row never leaves the
+ * device as a signature.
+ * p, q, dp, dq and qinv are SECRETS.  The chains run fixed 4-bit windows over all 2 pbytes digits of dp and dq: the sequence of
+ * products is a function of the set's pbytes alone, whatever the keys; the ADDRESS of the table row a window multiplies by does depend
+ * on the digit, and nothing else does.  A set's device rows, and the scratch a call left m2, h and its tables in, are overwritten
+ * before they are freed or reused; no error string ever contains key material.
+ *
+ * bftkv_gpu_rsa_signer_create: n_keys keys, 1 <= n_keys <= 2^16; keys_n [n_keys][nbytes], keys_e [n_keys], 1 <= nbytes <= 256;
+ * p, q, dp, dq, qinv [n_keys][pbytes] each, 1 <= pbytes <= 128.  Rows are big-endian and may hold any value of their width.  A key is
+ * REFUSED (counted in n_refused_out, no error) when n is even, or when p or q is even or below 3.  Ownership, locking, handle space and
+ * error codes are those of the other key sets, in a handle space of its own: created and destroyed on the root context (a fork:
+ * BFTKV_E_STATE), read by its forks and batcher lanes, a destroyed handle BFTKV_E_INVALID and handed out again by a later create; a
+ * failed build leaves nothing behind (*set_out = -1). */
+#define BFTKV_TH_CHECK_FAILED 4
+#define BFTKV_RSA_SIGN_LAUNCH 16384u      /* signatures of one chain launch: a larger call is split (its answers do not depend on that) */
+int bftkv_gpu_rsa_signer_create(bftkv_gpu_ctx* ctx, uint32_t n_keys, const uint8_t* keys_n, const uint32_t* keys_e, uint32_t nbytes,
+                                const uint8_t* p, const uint8_t* q, const uint8_t* dp, const uint8_t* dq, const uint8_t* qinv, uint32_t pbytes,
+                                int* set_out);
+int bftkv_gpu_rsa_signer_destroy(bftkv_gpu_ctx* ctx, int set);
+/* any of the outputs may be NULL */
+int bftkv_gpu_rsa_signer_info(bftkv_gpu_ctx* ctx, int set, uint32_t* n_keys_out, uint32_t* n_refused_out, uint32_t* nbytes_out,
+                              uint32_t* pbytes_out);
+/* digests [n_ops][dlen], key_idx [n_ops] (NULL: key 0; an index past the set is clamped to the last key) -> sig_out [n_ops][nbytes of
+ * the set], status_out [n_ops] as above.  BFTKV_E_INVALID for the call on an unknown hash_id, a dlen that is not the hash's size
+ * (hash_id 0: 1 <= dlen <= 64), a bad handle or a NULL array: every status BFTKV_TH_FAILED and every output byte 0 (under a NULL
+ * context or a bad handle the width of the rows is unknown: they are left alone).  n_ops = 0 returns 0; nothing past n_ops is written. */
+int bftkv_gpu_rsa_sign_keyset(bftkv_gpu_ctx* ctx, int set, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen,
+                              const uint32_t* key_idx, uint8_t* sig_out, uint8_t* status_out);
+/* same with the per-signature arrays resident in HBM: nothing is read from host memory, asynchronous on the context's stream */
+int bftkv_gpu_rsa_sign_keyset_dev(bftkv_gpu_ctx* ctx, int set, uint32_t n_ops, const uint8_t* digests, uint32_t hash_id, uint32_t dlen,
+                                  const uint32_t* key_idx, uint8_t* sig_out, uint8_t* status_out);
+/* Self-test: the same chains and recombination on a caller's c [n_ops][nbytes] of ANY value of the width, without padding and without
+ * the check: out = m2 + h q with m1 = (c mod p)^dp mod p, m2 = (c mod q)^dq mod q.  (The padded em cannot be steered to the operands at
+ * which the recombination can go wrong.)  status: BFTKV_TH_FENCED for a refused key, BFTKV_TH_CHECK_FAILED for a value that does not fit
+ * nbytes, zeroes either way; else BFTKV_TH_OK.  Host arrays. */
+int bftkv_gpu_selftest_rsa_crt(bftkv_gpu_ctx* ctx, int set, uint32_t n_ops, const uint8_t* c, const uint32_t* key_idx, uint8_t* out,
+                               uint8_t* status_out);
 
 /* ---- threshold password authentication, TPA (docs/parity.md "Password authentication (crypto/auth)") ------------------------
  * The phase computations of crypto/auth/auth.go, from request bytes to response fields in one device pass:

@@ -944,6 +944,275 @@ def _tpa_run(which):
     return run
 
 
+# ---- rsa_sign_keyset and selftest_rsa_crt: one signer set of 256-byte rows and 128-byte private parts ------------------------
+TH_OK, TH_NO_INVERSE, TH_FENCED, TH_INVALID_INPUT, TH_CHECK_FAILED = 0, 1, 2, 3, 4
+RSAS_SIGS_PER_BLOCK = 64 // 2         # rsa_sign_kernels.hip: QUADS_PER_BLOCK / 2, two quads of a 256-thread block per signature
+
+
+@functools.lru_cache(maxsize=None)
+def _rsas_keys(kind):
+    """good: two honest RSA-2048 keys, none of them a key of _rsav_pool (keys 2 and 3) or of moduli("bad") (keys 0 and 1).  bad: the
+    same with qinv + 1: every signature fails the check.  other: two more honest keys (the self-test's `bad`).  refused: key 0 with
+    an even p (fenced), and an honest 368-bit key, under which SHA-256 meets the length rule (k = 46 < 51 + 11)."""
+    import rsa_sign_cases as SC
+    import rsa_sign_ref as R
+    ks = [R.key_from_primes(k["p"], k["q"], k["e"]) for k in load_keys("rsa2048", 8)[4:8]]
+    if kind == "good":
+        return tuple(ks[:2])
+    if kind == "bad":
+        return tuple(SC._break(k, "qinv+1") for k in ks[:2])
+    if kind == "other":
+        return tuple(ks[2:4])
+    small = load_keys("rsa368", 1)[0]
+    return (SC._refuse(ks[0], "even_p"), R.key_from_primes(small["p"], small["q"], small["e"]))
+
+
+@functools.lru_cache(maxsize=None)
+def _rsas_pool(kind):
+    """POOL SHA-256 digests, the keys alternating: (digest, key index, status, s).  refused: the even rows are fenced, the odd ones
+    refused by the length rule -- neither is the status of `good` (0) or of `bad` (4)."""
+    import rsa_sign_ref as R
+    rng = np.random.default_rng(_seed("rsas", kind, 0))
+    keys = _rsas_keys(kind)
+    ops = []
+    for j in range(POOL):
+        dg = rng.bytes(32)
+        ops.append((dg, j % 2) + R.sign(keys[j % 2], 8, dg, 256))
+    return keys, tuple(ops)
+
+
+def _rsas_build(kind, n):
+    keys, pool = _rsas_pool(kind)
+    off = 0 if n == SIZES[0] else 5
+    return {"keys": [k._asdict() for k in keys], "ops": [pool[(i + off) % POOL] for i in range(n)]}
+
+
+def _rsas_ref(inp):
+    return {"sig": [o[3] for o in inp["ops"]], "status": np.array([o[2] for o in inp["ops"]], dtype=np.uint8)}
+
+
+def _rsas_run(ctx, inp, handle):
+    sig, st = ctx.rsa_sign_keyset(handle, [o[0] for o in inp["ops"]], 8, [o[1] for o in inp["ops"]])
+    return {"sig": _b2i(sig), "status": st.copy(), "sig_rows": sig}           # (the rows as the wrapper allocated them: section (f))
+
+
+def _rsas_setup(ctx, inp):
+    return ctx.rsa_signer_create(inp["keys"], nbytes=256, pbytes=128)
+
+
+@functools.lru_cache(maxsize=None)
+def _crt_pool(kind):
+    """POOL values below n through the chains and the recombination alone (no padding, no check): there is no per-operation
+    failure, `bad` is other values under the other two keys."""
+    import rsa_sign_ref as R
+    rng = np.random.default_rng(_seed("rsa_crt", kind, 0))
+    keys = _rsas_keys("good" if kind == "good" else "other")
+    ops = []
+    for j in range(POOL):
+        c = _rnd(rng, keys[j % 2].n) or 2
+        ops.append((c, j % 2) + R.selftest(keys[j % 2], c, 256))
+    return keys, tuple(ops)
+
+
+def _crt_build(kind, n):
+    keys, pool = _crt_pool(kind)
+    off = 0 if n == SIZES[0] else 5
+    return {"keys": [k._asdict() for k in keys], "ops": [pool[(i + off) % POOL] for i in range(n)]}
+
+
+def _crt_ref(inp):
+    return {"out": [o[3] for o in inp["ops"]], "status": np.array([o[2] for o in inp["ops"]], dtype=np.uint8)}
+
+
+def _crt_run(ctx, inp, handle):
+    out, st = ctx.selftest_rsa_crt(handle, [o[0] for o in inp["ops"]], [o[1] for o in inp["ops"]])
+    return {"out": _b2i(out), "status": st.copy(), "out_rows": out}
+
+
+# ---- rsa_partial_sign --------------------------------------------------------------------------------------------------------
+PSIGN_EXP_LEN = 64
+PSIGN_WIDTHS = (64, 33, 17)           # exp_used: three widths, so that the host's longest-first order is a real permutation
+
+
+def _psign_t(rng, n, bad):
+    """T of 51 bytes (the length of a SHA-256 DigestInfo) whose em is a unit mod n, or (bad) a multiple of 3: a counter in its tail"""
+    import math
+    import rsa_psign_ref as P
+    head = rng.bytes(47)
+    for ctr in range(1 << 16):
+        t = head + ctr.to_bytes(4, "big")
+        em = P.emsa_encode(t, n)
+        if math.gcd(em, n) == (3 if bad else 1):
+            return t
+    raise ValueError("no T found")
+
+
+def _psign_build(kind, n):
+    """n fragments over requests of three and two fragments in turn, handed over in a shuffled order (frag_req is no sorted list).
+    good: under moduli("good"), every third request without a negative fragment, both signs in each of the others.  bad: every
+    fragment negative (three different non-zero sign bytes), under 3 x a 2041-bit modulus and 15 x it, with 3 | em: no inverse.
+    positive: `good`'s shape with every sign byte 0 -- the inversion kernel is not launched at all."""
+    rng = np.random.default_rng(_seed("psign", kind, n))
+    mods = [composite(), composite() * 5] if kind == "bad" else list(moduli("good"))
+    ts, frags = [], []
+    while len(frags) < n:
+        r = len(ts)
+        ts.append(_psign_t(rng, mods[r % 2], kind == "bad"))
+        for j in range(min(2 + (r + 1) % 2, n - len(frags))):
+            used = PSIGN_WIDTHS[(r + j) % 3]
+            mag = int.from_bytes(rng.bytes(used), "big") | (1 << (8 * used - 1))
+            if kind == "bad":
+                sb = (1, 0xFF, 2)[j]
+            elif kind == "positive" or r % 3 == 2:
+                sb = 0
+            else:
+                sb = (1, 0xFF, 0)[(r + j) % 3]
+            frags.append((r, sb, mag, used))
+    frags = [frags[int(i)] for i in rng.permutation(n)]
+    return {"t": ts, "mods": mods, "mod_idx": [r % 2 for r in range(len(ts))], "frags": frags}
+
+
+def _psign_ref(inp):
+    import rsa_psign_ref as P
+    res = [P.sign(inp["t"][r], inp["mods"][inp["mod_idx"][r]], [(sb, mag)])[0] for r, sb, mag, _ in inp["frags"]]
+    return {"out": [v for _, v in res], "status": np.array([s for s, _ in res], dtype=np.uint8)}
+
+
+def _psign_run(ctx, inp, handle=None):
+    ts, fr = inp["t"], inp["frags"]
+    t = np.full((len(ts), max(len(b) for b in ts)), 0xEE, dtype=np.uint8)      # what follows T in its row is not zero
+    for i, b in enumerate(ts):
+        t[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+    out, st = ctx.rsa_partial_sign(t, [len(b) for b in ts], _i2b(inp["mods"], 256), _i2b([f[2] for f in fr], PSIGN_EXP_LEN),
+                                   np.array([f[1] for f in fr], dtype=np.uint8), inp["mod_idx"], [f[0] for f in fr], [f[3] for f in fr])
+    return {"out": _b2i(out), "status": st.copy(), "out_rows": out}
+
+
+# ---- threshold DSA / ECDSA signing: the share answers and phase 3 --------------------------------------------------------------
+TSIG_M = 4                            # shares per request
+TSIG_FIELDS = ("ri", "vi", "ki", "ci")
+
+
+def _tsig_requests(q, seeds, keep):
+    """the requests of the classes `keep` admits, those with every share at or above q from row 5 on (where both sizes of a character
+    hold them: _tsig_rows)"""
+    import tsig_share_cases as K
+    cases = [(lb, sh) for s in seeds for lb, sh in K.requests(q, 32, TSIG_M, 4, K.windows_of(q, 4), seed=s) if keep(lb)]
+    above, rest = [sh for lb, sh in cases if lb == "s:above_q"], [sh for lb, sh in cases if lb != "s:above_q"]
+    return rest[:5] + above + rest[5:]
+
+
+def _tsig_rows(n):
+    off = 0 if n == SIZES[0] else 5
+    return [i + off for i in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def _tdsa_pool(kind):
+    """good: every class of tests/tsig_share_cases.py under group 0 of its two groups (1024 / 160 bits in rows of 256 / 32 bytes), less
+    the two whose columns sum to 0 (a result row of a good operation is never zero).  bad: under group 1 (2048 / 256 bits), less the
+    classes with an answer that does not depend on the group (ai = 0: ri = 1; all sums 0 or 1; m shares of q - 1 in every column:
+    vi = m^2 - m); its `above_q` requests hold shares in [q, 2^256).  No row of one appears in the other
+    (tests/test_state_reference.py)."""
+    import tsig_share_cases as K
+    import tsig_share_ref as R
+    gs = [K.dsa_groups()[name] for name in K.DSA_NAMES]
+    gi = 0 if kind == "good" else 1
+    drop = ("s:sum_0", "s:sum_q") if kind == "good" else ("s:sum_0", "s:sum_q", "s:sum_1", "s:wrap", "a:zero")
+    reqs = _tsig_requests(gs[gi].q, (11, 12) if kind == "good" else (13, 14), lambda lb: lb not in drop)[:SIZES[1] + 5]
+    G = R.dsa_group(gs[gi].p, gs[gi].q, gs[gi].g, 256, 32)
+    ans = [R.phase2(G, sh) for sh in reqs]
+    return gs, gi, reqs, [(int.from_bytes(a.ri, "big"), a.vi, a.ki, a.ci) for a in ans]
+
+
+def _tdsa_build(kind, n):
+    gs, gi, reqs, ans = _tdsa_pool(kind)
+    rows = _tsig_rows(n)
+    return {"groups": [(g.p, g.q, g.g) for g in gs], "keys": [(i, g.y) for i, g in enumerate(gs)], "gi": gi, "reqs": [reqs[i] for i in rows],
+            "want": [ans[i] for i in rows]}
+
+
+def _tsig_ref(inp):
+    out = {f: [w[k] for w in inp["want"]] for k, f in enumerate(TSIG_FIELDS)}
+    out["status"] = np.zeros(len(inp["want"]), dtype=np.uint8)
+    return out
+
+
+def _tdsa_setup(ctx, inp):
+    return ctx.dsa_keyset_create(inp["keys"], inp["groups"], window_bits=4, pbytes=256, qbytes=32)
+
+
+def _tdsa_run(ctx, inp, handle):
+    import tsig_share_cases as K
+    ri, vi, ki, ci, st = ctx.tdsa_share(handle, K.shares_array(inp["reqs"], 32), group_idx=[inp["gi"]] * len(inp["reqs"]))
+    return {"ri": _b2i(ri), "vi": _b2i(vi), "ki": _b2i(ki), "ci": _b2i(ci), "status": st.copy(), "ri_rows": ri, "vi_rows": vi, "ki_rows": ki, "ci_rows": ci}
+
+
+@functools.lru_cache(maxsize=None)
+def _tecdsa_pool(kind):
+    """P-256 (P-521 costs the device 14 ms a call whatever its size, docs/history.md, and the restatement in proportion).  good: every
+    class but the two zero sums.  bad: the classes with a random ai alone -- one group serves both kinds, so a fixed scalar (0, 1, 2,
+    q - 1, one digit, ...) would put the same ri into both."""
+    import tsig_share_ref as R
+    E, c = _curve()
+    n = c["n"]
+    if kind == "good":
+        reqs = _tsig_requests(n, (21, 22), lambda lb: lb not in ("s:sum_0", "s:sum_q"))
+    else:
+        reqs = _tsig_requests(n, (31, 32, 33, 34, 35), lambda lb: lb.startswith("a:random") or lb == "s:above_q")
+    reqs = reqs[:SIZES[1] + 5]
+    ans = []
+    for sh in reqs:
+        ki, ai, bi, ci = R.fold(sh, n)
+        ans.append((E.calculate_partial_r(c, ai), R.vi_of(n, ki, ai, bi), ki, ci))
+    return reqs, ans
+
+
+def _tecdsa_build(kind, n):
+    reqs, ans = _tecdsa_pool(kind)
+    rows = _tsig_rows(n)
+    return {"reqs": [reqs[i] for i in rows], "want": [ans[i] for i in rows]}
+
+
+def _tecdsa_run(ctx, inp, handle=None):
+    import tsig_share_cases as K
+    ri, vi, ki, ci, st = ctx.tecdsa_share(K.shares_array(inp["reqs"], 32), _curve()[1])
+    return {"ri": [bytes(r) for r in ri], "vi": _b2i(vi), "ki": _b2i(ki), "ci": _b2i(ci), "status": st.copy(), "ri_rows": ri, "vi_rows": vi, "ki_rows": ki,
+            "ci_rows": ci}
+
+
+@functools.lru_cache(maxsize=None)
+def partial_s_orders(kind):
+    """Two odd orders in rows of 32 bytes.  good: the 256-bit q of the 2048-bit DSA group and P-256's N.  bad: the 160-bit q of the
+    1024-bit group and P-224's N, so that there is room for operands at or above q."""
+    import tsig_share_cases as K
+    E, c = _curve()
+    if kind == "good":
+        return (K.dsa_groups()["dsa2048"].q, c["n"])
+    return (K.dsa_groups()["dsa1024"].q, E.CURVES["P-224"]["n"])
+
+
+def _partial_s_build(kind, n):
+    """(m, r, y, k, c) per request: below q (good); every operand in [q, 2^256) (bad)"""
+    import random
+    rng = random.Random(_seed("partial_s", kind, n))
+    qs = partial_s_orders(kind)
+    idx = [i % 2 for i in range(n)]
+    return {"q": list(qs), "idx": idx, "ops": [tuple(rng.randrange(qs[i]) if kind == "good" else rng.randrange(qs[i], 1 << 256) for _ in range(5)) for i in idx]}
+
+
+def _partial_s_ref(inp):
+    import tsig_share_ref as R
+    return {"si": [R.phase3(inp["q"][i], r, y, m, k, c) for (m, r, y, k, c), i in zip(inp["ops"], inp["idx"])],
+            "status": np.zeros(len(inp["ops"]), dtype=np.uint8)}
+
+
+def _partial_s_run(ctx, inp, handle=None):
+    m, r, y, k, c = (_i2b([o[j] for o in inp["ops"]], 32) for j in range(5))
+    si, st = ctx.tsig_partial_s(m, r, y, k, c, _i2b(inp["q"], 32), inp["idx"])
+    return {"si": _b2i(si), "status": st.copy(), "si_rows": si}
+
+
 ENTRIES = (
     Entry("modmul_product", "threshold", _modmul_build, _modmul_ref, _modmul_run, ("out",), None),
     Entry("lagrange_combine_small", "threshold", _lagrange_build("small"), _lagrange_ref, _lagrange_run, ("out", "status"), None),
@@ -965,9 +1234,16 @@ ENTRIES = (
     Entry("tpa_yi", "tpa", _tpa_build, _tpa_ref("yi"), _tpa_run("yi"), ("out",), None),
     Entry("tpa_bi", "tpa", _tpa_build, _tpa_ref("bi"), _tpa_run("bi"), ("out", "keys", "mac"), None),
     Entry("tpa_ni", "tpa", _tpa_build, _tpa_ref("ni"), _tpa_run("ni"), ("keys", "mac"), None),
+    Entry("rsa_sign_keyset", "sign", _rsas_build, _rsas_ref, _rsas_run, ("sig", "status"), _rsas_setup),
+    Entry("rsa_crt_selftest", "sign", _crt_build, _crt_ref, _crt_run, ("out",), _rsas_setup),
+    Entry("rsa_partial_sign", "sign", _psign_build, _psign_ref, _psign_run, ("out", "status"), None),
+    Entry("tdsa_share", "sign", _tdsa_build, _tsig_ref, _tdsa_run, TSIG_FIELDS, _tdsa_setup),
+    Entry("tecdsa_share", "sign", _tecdsa_build, _tsig_ref, _tecdsa_run, TSIG_FIELDS, None),
+    Entry("tsig_partial_s", "sign", _partial_s_build, _partial_s_ref, _partial_s_run, ("si",), None),
 )
 ENTRY = {e.name: e for e in ENTRIES}
 VERIFY = tuple(e.name for e in ENTRIES if "valid" in e.compared)      # these also come as kind "invalid"
+THIRD_KIND = {"rsa_sign_keyset": "refused", "rsa_partial_sign": "positive"}      # the signing entries' third kinds
 
 
 @functools.lru_cache(maxsize=None)

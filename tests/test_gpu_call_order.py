@@ -395,6 +395,59 @@ def test_merely_invalid_operations_between_good_and_bad(name):
             check_op(run_op(ctx, name, pk, 141, hs), name, pk, 141, (sk, 70, "->"))
 
 
+@pytest.mark.parametrize("name", sorted(S.THIRD_KIND))
+def test_refused_signatures_and_positive_fragments_between_good_and_bad(name):
+    """The signing entries' third kinds.  rsa_sign_keyset `refused` -- fenced under an even-p key, refused by the length rule under a
+    368-bit one, in turn: behind good(141) a stale check byte would let a row out, behind bad(141) a stale rule byte would read 0.
+    rsa_partial_sign `positive` -- no negative fragment, so the inversion kernel is not launched: behind bad(141) its inverse rows and
+    no-inverse bytes are the predecessor's but for their clear.  And the reverse: good(70) and bad(70) behind the third kind's 141."""
+    third = S.THIRD_KIND[name]
+    check_op(op_baseline(name, third, 70), name, third, 70, "first call")
+    for pk, sk in (("good", third), ("bad", third), (third, "good"), (third, "bad")):
+        with fresh(keyring=False) as (ctx, _):
+            hs = {}
+            check_op(run_op(ctx, name, pk, 141, hs), name, pk, 141, "first call")
+            check_op(run_op(ctx, name, sk, 70, hs), name, sk, 70, (pk, 141, "->"))
+            check_op(run_op(ctx, name, pk, 141, hs), name, pk, 141, (sk, 70, "->"))
+
+
+@pytest.mark.parametrize("name,n", [("rsa_sign_keyset", 1), ("rsa_sign_keyset", S.RSAS_SIGS_PER_BLOCK + 1), ("rsa_partial_sign", 1)])
+def test_padding_pairs_of_the_last_block_leave_nothing(name, n):
+    """One signature (31 padding pairs re-run it), one more than a block holds (the second block: one signature, 31 padding pairs), one
+    fragment (63 padding quads): first on a fresh context (the baseline), then behind bad(141), whose scratch is as wide and whose
+    every row ended the other way.  Both halves: the n answers are the reference's and the baseline's; nothing of a padding pair's run
+    shows in them."""
+    assert S.RSAS_SIGS_PER_BLOCK == 32
+    check_op(op_baseline(name, "good", n), name, "good", n, "first call")
+    with fresh(keyring=False) as (ctx, _):
+        hs = {}
+        check_op(run_op(ctx, name, "bad", 141, hs), name, "bad", 141, "first call")
+        check_op(run_op(ctx, name, "good", n, hs), name, "good", n, ("bad", 141, "->"))
+        check_op(run_op(ctx, name, "bad", 141, hs), name, "bad", 141, ("good", n, "->"))
+        check_op(run_op(ctx, name, "good", n, hs), name, "good", n, ("bad", 141, "-> again"))
+
+
+@pytest.mark.parametrize("name", ("rsa_sign_keyset", "tdsa_share"))
+def test_a_fork_reads_the_roots_sets_from_a_scratch_pool_of_its_own(name):
+    """good(70) on a fork behind bad(141) on the root (the fork's pool is fresh, the set's resident rows are the root's) and behind
+    bad(141) on the fork itself (its own pool, used), and the root's good(70) behind the fork's calls"""
+    with fresh(keyring=False) as (root, _):
+        hs = {}
+        for kind in ("bad", "good"):
+            run_op(root, name, kind, 70, hs)                 # the sets are created on the root: a fork may not
+        hs_used = dict(hs)
+        check_op(run_op(root, name, "bad", 141, hs), name, "bad", 141, "root")
+        fork = root.fork()
+        try:
+            check_op(run_op(fork, name, "good", 70, hs), name, "good", 70, ("root bad 141 ->", "fork"))
+            check_op(run_op(fork, name, "bad", 141, hs), name, "bad", 141, "fork")
+            check_op(run_op(fork, name, "good", 70, hs), name, "good", 70, ("fork bad 141 ->", "fork"))
+            check_op(run_op(root, name, "good", 70, hs), name, "good", 70, ("fork good 70 ->", "root"))
+        finally:
+            fork.close()
+        assert hs == hs_used                                 # no set was created behind the root's back
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_behind_the_141_operation_call_of_every_other_entry(name):
     """good(70) and bad(70) directly behind the 141-operation call of every OTHER entry, good and bad alternating: the pool hands
@@ -491,6 +544,7 @@ def test_device_forms_write_every_output_byte():
     """the _dev forms with the caller's device arrays filled with 0xA5: n_ops results and status bytes are written, nothing behind them"""
     import ctypes as C
     import torch
+    import tsig_share_cases as K
     from bftkv_amd._native import _curve_bytes, _ints_to_be, _ptr
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")      # noqa: E731
     a5 = lambda *shape: torch.full(shape, 0xA5, dtype=torch.uint8, device="cuda:0")      # noqa: E731
@@ -562,3 +616,30 @@ def test_device_forms_write_every_output_byte():
                 if (name, kind) not in sets:
                     sets[name, kind] = S.ENTRY[name].setup(ctx, S.op_input(name, kind, n))
                 verdicts(name, lambda i, dg, dl, sg, ki, v, st, call=call, ks=sets[name, kind]: call(ks, dg, dl, sg, ki, v, st))
+            # the signing entries: RSA under a resident signer set, the share answers under a resident DSA key set and on P-256
+            for name in ("rsa_sign_keyset", "tdsa_share"):
+                if (name, kind) not in sets:
+                    sets[name, kind] = S.ENTRY[name].setup(ctx, S.op_input(name, kind, n))
+            i, want = S.op_input("rsa_sign_keyset", kind, n), S.op_reference("rsa_sign_keyset", kind, n)
+            dg = up(np.frombuffer(b"".join(o_[0] for o_ in i["ops"]), dtype=np.uint8).copy())
+            ki = up(np.array([o_[1] for o_ in i["ops"]], dtype=np.int32))
+            sig, st = a5(n + 1, 256), a5(n + 8)
+            ctx._check(lib.bftkv_gpu_rsa_sign_keyset_dev(h, sets["rsa_sign_keyset", kind], n, P(dg), 8, 32, P(ki), P(sig), P(st)), "rsa_sign_keyset_dev")
+            ctx.sync()
+            assert st.cpu().numpy()[:n].tolist() == want["status"].tolist() and (st[n:] == 0xA5).all(), kind
+            assert toi(sig[:n]) == want["sig"] and (sig[n:] == 0xA5).all(), kind
+            for name, rw in (("tdsa_share", 256), ("tecdsa_share", 65)):
+                i, want = S.op_input(name, kind, n), S.op_reference(name, kind, n)
+                sh = up(K.shares_array(i["reqs"], 32).reshape(-1))
+                ri, vi, ki, ci, st = a5(n + 1, rw), a5(n + 1, 32), a5(n + 1, 32), a5(n + 1, 32), a5(n + 8)
+                if name == "tdsa_share":
+                    gi = up(np.full(n, i["gi"], dtype=np.int32))
+                    rc = lib.bftkv_gpu_tdsa_share_dev(h, sets[name, kind], n, P(gi), S.TSIG_M, P(sh), P(ri), P(vi), P(ki), P(ci), P(st))
+                else:
+                    rc = lib.bftkv_gpu_tecdsa_share_dev(h, n, S.TSIG_M, P(sh), vp(cb_), bits, P(ri), P(vi), P(ki), P(ci), P(st))
+                ctx._check(rc, name + "_dev")
+                ctx.sync()
+                assert not st[:n].any() and (st[n:] == 0xA5).all(), (name, kind)
+                assert (toi(ri[:n]) if rw == 256 else [bytes(r) for r in ri[:n].cpu().numpy()]) == want["ri"] and (ri[n:] == 0xA5).all(), (name, kind)
+                for f, t in (("vi", vi), ("ki", ki), ("ci", ci)):
+                    assert toi(t[:n]) == want[f] and (t[n:] == 0xA5).all(), (name, kind, f)

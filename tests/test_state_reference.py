@@ -189,10 +189,13 @@ def test_complement_condition_of_the_pipeline_pairs():
 
 # ---- the other entry points ------------------------------------------------------------------------------------------------
 WORST = {"lagrange_combine_small": 1, "lagrange_combine_big": 1, "lagrange_combine_huge": 2, "dsa_calculate_r": 1, "modinv": 1, "ec_scalar_base_mult": 2,
-         "ecdsa_verify": 2, "ecdsa_verify_keyset": 2, "dsa_verify": 2, "dsa_verify_keyset": 2, "rsa_verify": 2, "rsa_verify_keyset": 2}
-"""The status every operation of `bad` ends with: 1 = no inverse (a composite modulus; v = 0 mod q), 2 = fenced (integers beyond
-2128 bits, a scalar of N or more, a key off the curve, a digest longer than the order, an even modulus).  ecdsa_calculate_r mixes
-both (a partial R off the curve; v = 0 mod N).  The entries that are not listed have no per-operation failure."""
+         "ecdsa_verify": 2, "ecdsa_verify_keyset": 2, "dsa_verify": 2, "dsa_verify_keyset": 2, "rsa_verify": 2, "rsa_verify_keyset": 2,
+         "rsa_sign_keyset": 4, "rsa_partial_sign": 1}
+"""The status every operation of `bad` ends with: 1 = no inverse (a composite modulus; v = 0 mod q; a negative fragment of a request
+whose em shares the factor 3 with its modulus), 2 = fenced (integers beyond 2128 bits, a scalar of N or more, a key off the curve,
+a digest longer than the order, an even modulus), 4 = the check failed (a signature under a key whose qinv is off by one: s^e != em,
+and no byte of s leaves the device).  ecdsa_calculate_r mixes both (a partial R off the curve; v = 0 mod N).  The entries that are
+not listed have no per-operation failure."""
 NAMES = [e.name for e in S.ENTRIES]
 
 
@@ -217,7 +220,7 @@ def test_good_succeeds_and_bad_ends_the_worst_way(name):
         else:
             assert "status" not in bad or not np.asarray(bad["status"]).any()
         if name in WORST or name == "ecdsa_calculate_r":                      # zeroes beside a status that is not 0
-            for f in ("out",):
+            for f in ("out", "sig"):
                 if f in bad:
                     assert all(_zero(v) for v in bad[f] if v is not S.UNCLAIMED), name
                     assert (name in ("lagrange_combine_small", "dsa_calculate_r")) == any(v is S.UNCLAIMED for v in bad[f]), name
@@ -263,6 +266,93 @@ def test_invalid_is_status_0_beside_validity_0_and_no_inverse_under_a_composite_
         assert (pred[f][:70] != succ[f]).all(), (name, a, b)
 
 
+def test_refused_signatures_are_fenced_and_invalid_input_in_turn():
+    """The third kind of rsa_sign_keyset: under an even-p key BFTKV_TH_FENCED (2), under a 368-bit key the length rule's
+    BFTKV_TH_INVALID_INPUT (3), alternating, zeroes beside both.  Against `good` (0) and against `bad` (4) the status byte differs
+    at every shared operation, and so does the row against `good`."""
+    assert S.THIRD_KIND["rsa_sign_keyset"] == "refused"
+    keys = S._rsas_keys("refused")
+    assert keys[0].p % 2 == 0 and keys[0].n % 2 == 1 and keys[1].n.bit_length() <= 408 and (keys[1].n.bit_length() + 7) // 8 < 51 + 11
+    assert keys[1].n == keys[1].p * keys[1].q and keys[1].p % 2 == 1 and keys[1].q % 2 == 1           # refused by the length alone
+    for n in S.SIZES:
+        r = S.op_reference("rsa_sign_keyset", "refused", n)
+        assert len(r["status"]) == n and set(r["status"].tolist()) == {S.TH_FENCED, S.TH_INVALID_INPUT}
+        assert (r["status"][0::2] == r["status"][0]).all() and (r["status"][1::2] == r["status"][1]).all() and r["status"][0] != r["status"][1]
+        assert not any(r["sig"])
+    for a, b in (("refused", "good"), ("good", "refused"), ("refused", "bad"), ("bad", "refused")):
+        pred, succ = S.op_reference("rsa_sign_keyset", a, 141), S.op_reference("rsa_sign_keyset", b, 70)
+        assert (pred["status"][:70] != succ["status"]).all(), (a, b)
+        if "good" in (a, b):
+            assert all(x != y for x, y in zip(pred["sig"][:70], succ["sig"])), (a, b)
+
+
+def test_positive_fragments_need_no_inverse():
+    """The third kind of rsa_partial_sign: no negative fragment in the whole call, status 0, no row zero.  Against `bad` status
+    and row differ at every shared fragment, against `good` the row."""
+    assert S.THIRD_KIND["rsa_partial_sign"] == "positive"
+    for n in S.SIZES:
+        i, r = S.op_input("rsa_partial_sign", "positive", n), S.op_reference("rsa_partial_sign", "positive", n)
+        assert len(i["frags"]) == n and not any(sb for _, sb, _, _ in i["frags"])
+        assert not r["status"].any() and all(r["out"])
+    for a, b in (("positive", "good"), ("good", "positive"), ("positive", "bad"), ("bad", "positive")):
+        pred, succ = S.op_reference("rsa_partial_sign", a, 141), S.op_reference("rsa_partial_sign", b, 70)
+        assert all(x != y for x, y in zip(pred["out"][:70], succ["out"])), (a, b)
+        if "bad" in (a, b):
+            assert (pred["status"][:70] != succ["status"]).all(), (a, b)
+
+
+def test_the_partial_sign_calls_have_the_shape_the_host_sort_needs():
+    """Two or three fragments per request, handed over out of request order; exp_used over three widths, every magnitude exactly as
+    wide as it says; good: both signs, and at least a quarter of the requests without a negative fragment; bad: every fragment negative
+    and non-zero under a modulus of at most 2048 bits that 3 divides."""
+    for kind in ("good", "bad", "positive"):
+        for n in S.SIZES + (1,):
+            i = S.op_input("rsa_partial_sign", kind, n)
+            per = {}
+            for r, sb, mag, used in i["frags"]:
+                per.setdefault(r, []).append(sb)
+                assert used in S.PSIGN_WIDTHS and (mag.bit_length() + 7) // 8 == used and mag > 0
+            assert sorted(per) == list(range(len(i["t"]))) and all(len(t) == 51 for t in i["t"])
+            if n == 1:
+                assert kind == "positive" or i["frags"][0][1] != 0                      # the one-fragment call takes the inversion
+                continue
+            assert set(len(per[r]) for r in sorted(per)[:-1]) == {2, 3} and len(per) < n
+            assert [f[0] for f in i["frags"]] != sorted(f[0] for f in i["frags"])
+            assert {f[3] for f in i["frags"]} == set(S.PSIGN_WIDTHS)
+            assert [f[3] for f in i["frags"]] != sorted((f[3] for f in i["frags"]), reverse=True)      # the longest-first order moves rows
+            if kind == "good":
+                assert {bool(sb) for v in per.values() for sb in v} == {False, True}
+                assert 4 * sum(not any(v) for v in per.values()) >= len(per)
+            elif kind == "bad":
+                assert all(sb for v in per.values() for sb in v) and all(m % 3 == 0 and m % 2 == 1 and m.bit_length() <= 2048 for m in i["mods"])
+
+
+def test_the_share_requests_of_the_two_kinds():
+    """tdsa_share: good under group 0, bad under group 1, with share columns at or above q in `bad`; tecdsa_share: two disjoint
+    request pools on one curve; tsig_partial_s: two odd orders per kind, the operands of `bad` at or above q."""
+    for n in S.SIZES:
+        g, b = S.op_input("tdsa_share", "good", n), S.op_input("tdsa_share", "bad", n)
+        assert (g["gi"], b["gi"]) == (0, 1) and g["groups"] == b["groups"] and len(g["groups"]) == 2
+        assert all(len(sh) == S.TSIG_M for sh in g["reqs"] + b["reqs"])
+        q1 = b["groups"][1][1]
+        assert any(all(v >= q1 for tup in sh for v in tup) for sh in b["reqs"])
+        g, b = S.op_input("tecdsa_share", "good", n), S.op_input("tecdsa_share", "bad", n)
+        assert not {repr(sh) for sh in g["reqs"]} & {repr(sh) for sh in b["reqs"]}
+        g, b = S.op_input("tsig_partial_s", "good", n), S.op_input("tsig_partial_s", "bad", n)
+        assert not set(g["q"]) & set(b["q"]) and all(q % 2 == 1 and q.bit_length() <= 256 for q in g["q"] + b["q"]) and len(set(g["q"] + b["q"])) == 4
+        assert all(v < g["q"][i] for o, i in zip(g["ops"], g["idx"]) for v in o)
+        assert all(b["q"][i] <= v < 1 << 256 for o, i in zip(b["ops"], b["idx"]) for v in o)
+    assert S.partial_s_orders("good")[0].bit_length() == 256 and S.partial_s_orders("good")[1] == S._curve()[1]["n"]
+
+
+def test_no_signature_of_the_signing_entry_is_a_signature_of_the_verify_pool():
+    """rsa_sign_keyset behind rsa_verify (and the reverse) reuses 256-byte rows: the two entries share no key, so no signature row"""
+    vkeys, vops = S._rsav_pool("good")
+    assert not {k.n for kind in ("good", "bad", "other", "refused") for k in S._rsas_keys(kind)} & ({n for n, _ in vkeys} | set(S.moduli("bad")))
+    theirs = {int.from_bytes(sg, "big") for _, sg, _, _ in vops}
+    assert not set(S.op_reference("rsa_sign_keyset", "good", 141)["sig"]) & theirs and len(theirs) == S.POOL
+
+
 def test_independent_restatements_of_the_good_answers():
     """The references come from the oracle / restatement modules the tests of each entry use; here the cheap ones are checked once more
     from their defining property."""
@@ -287,3 +377,31 @@ def test_independent_restatements_of_the_good_answers():
     assert all(math.prod(xs[1:]) >= 1 << 31 for xs in i["xs"])                         # the big path, not the 31-bit one
     i = S.op_input("lagrange_combine_small", "good", 141)
     assert all(abs(math.prod(x for x in xs if x != xj)) < 1 << 31 and abs(math.prod(x - xj for x in xs if x != xj)) < 1 << 31 for xs in i["xs"] for xj in xs)
+    # the signing entries: a good signature verifies; a partial signature is em^mag or its inverse; no bad request's em is a unit
+    i, r = S.op_input("rsa_sign_keyset", "good", 70), S.op_reference("rsa_sign_keyset", "good", 70)
+    for (dg, k, st, _), sig in list(zip(i["ops"], r["sig"]))[:12]:
+        key = i["keys"][k]
+        assert st == 0 and pow(sig, key["e"], key["n"]).to_bytes(256, "big") == V.em(256, 8, dg)
+    i, r = S.op_input("rsa_crt_selftest", "good", 70), S.op_reference("rsa_crt_selftest", "good", 70)
+    for (c, k, st, _), out in list(zip(i["ops"], r["out"]))[:12]:
+        key = i["keys"][k]
+        d = pow(key["e"], -1, (key["p"] - 1) * (key["q"] - 1))
+        assert st == 0 and c < key["n"] and out == pow(c, d, key["n"])               # an honest key: the CRT value is c^d mod n
+    import rsa_psign_ref as P
+    i, r = S.op_input("rsa_partial_sign", "good", 70), S.op_reference("rsa_partial_sign", "good", 70)
+    seen = set()
+    for (req, sb, mag, _), out in zip(i["frags"], r["out"]):
+        N = i["mods"][i["mod_idx"][req]]
+        em = P.emsa_encode(i["t"][req], N)
+        assert out * pow(em, mag, N) % N == 1 if sb else out == pow(em, mag, N)
+        seen.add(bool(sb))
+    assert seen == {False, True}
+    i = S.op_input("rsa_partial_sign", "bad", 70)
+    assert all(math.gcd(P.emsa_encode(t, i["mods"][k]), i["mods"][k]) == 3 for t, k in zip(i["t"], i["mod_idx"]))
+    i, r = S.op_input("tsig_partial_s", "bad", 70), S.op_reference("tsig_partial_s", "bad", 70)
+    assert all(si == ((r_ * y + m) * k + c) % i["q"][j] for (m, r_, y, k, c), j, si in zip(i["ops"], i["idx"], r["si"]))
+    i, r = S.op_input("tdsa_share", "bad", 70), S.op_reference("tdsa_share", "bad", 70)
+    p, q, g = i["groups"][1]
+    for sh, ri, vi, ki, ci in list(zip(i["reqs"], r["ri"], r["vi"], r["ki"], r["ci"]))[:12]:
+        k, a, b, c = (sum(col) % q for col in zip(*sh))
+        assert (ri, vi, ki, ci) == (pow(g, a, p), (k * a + b) % q, k, c)

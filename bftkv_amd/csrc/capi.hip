@@ -38,6 +38,7 @@
 #include "ec_kernels.hip"
 #include "dsa_verify_kernels.hip"
 #include "rsa_verify_kernels.hip"
+#include "window_chain.h"
 #include "tpa_kernels.hip"
 #include "rsa_psign_kernels.hip"
 #include "tsig_share_kernels.hip"

@@ -84,7 +84,7 @@ int psign_run(bftkv_gpu_ctx* c, const PsignOut& o, uint32_t n_reqs, const uint8_
   if ((rc = dev_alloc(c, sb, (size_t)n_reqs * MONT_N * 4, &d_em, false)) || (rc = dev_alloc(c, sb, (size_t)n_reqs * MONT_N * 4, &d_inv, true)) ||
       (rc = dev_alloc(c, sb, (size_t)n_reqs + 8, &d_ref, false)) || (rc = dev_alloc(c, sb, (size_t)n_reqs + 8, &d_noinv, true)) ||
       (rc = dev_alloc(c, sb, (size_t)n_frags * MONT_N * 4, &d_out, false)) || (rc = dev_alloc(c, sb, (size_t)n_frags + 8, &d_st, false)) ||
-      (rc = dev_alloc(c, sb, tab_quads * TPA_ENT * MONT_N * 4, &d_tab, false)) || (rc = dev_alloc(c, sb, (size_t)n_frags * nbytes, &d_bytes, false)))
+      (rc = dev_alloc(c, sb, tab_quads * CHAIN_ENT * MONT_N * 4, &d_tab, false)) || (rc = dev_alloc(c, sb, (size_t)n_frags * nbytes, &d_bytes, false)))
     return rc;
   hipLaunchKernelGGL(k_psign_em, dim3((uint32_t)(((size_t)n_reqs * MONT_N + 255) / 256)), dim3(256), 0, s, n_reqs, (const uint8_t*)d_t, t_cap, (const uint32_t*)d_tl,
                      (const uint32_t*)d_rmod, (const uint8_t*)d_mods, nbytes, (uint32_t*)d_em, (uint8_t*)d_ref);

@@ -2,10 +2,10 @@
 // key fragments in, the partial signatures of serializePartialSignature out, without a host step in between.
 //   k_psign_em     em = 00 01 FF .. 00 | T of every request as radix-2^28 limbs, and its refusal byte (rsa_psign.h)
 //   k_modinv       (threshold_kernels.hip, gated) m^-1 mod N and the no-inverse byte, ONCE per request that has a negative fragment
-//   k_psign_pow    m^mag or (m^-1)^mag mod N, mag of up to 8200 bytes: k_tpa_pow's fixed 4-bit windows, a window count per WAVE
+//   k_psign_pow    m^mag or (m^-1)^mag mod N, mag of up to 8200 bytes: window_chain's fixed 4-bit windows, a window count per WAVE
 // The rules: docs/parity.md, "Threshold RSA signing (rsaContext.Sign)".
 #pragma once
-// (kernels.hip, threshold_kernels.hip and tpa_kernels.hip are included before this file by capi.hip)
+// (kernels.hip, threshold_kernels.hip, window_chain.h and tpa_kernels.hip are included before this file by capi.hip)
 #include "rsa_psign.h"
 
 namespace bftkv {
@@ -26,19 +26,22 @@ __global__ void k_psign_em(uint32_t n_reqs, const uint8_t* __restrict__ t /*[n_r
 // out[frag] = base ^ mag mod N for one CHAIN per quad.  Chain c of the call is fragment order[c]; the host hands the chains over
 // longest first, so that the quads of a wave agree on their width, but no answer depends on that order.
 //
-// k_tpa_pow's schedule (tpa_kernels.hip): the table b^0 .. b^15 in Montgomery form goes to global memory, written and re-read by the
-// same lanes, then every window is 4 squarings and ONE multiplication by the row its digit names -- the row of a zero digit is the
-// Montgomery one, so nothing is skipped and nothing selected.  Three things differ:
+// The chain is window_chain (window_chain.h, with what depends on a secret and what does not), as k_tpa_pow's.  Three things differ:
 //   * the base row is m or m^-1 of the fragment's request, by the fragment's sign: an address, like the table row;
 //   * the window count is the WAVE's: 2 x the widest exp_used among its 16 quads.  A narrower chain meets zero digits first, which is
 //     what left-padding its magnitude to the wave's width gives: 1 * 1 = 1 in Montgomery form, so its answer is unchanged, and the
-//     program counter stays wave-uniform (the two multiplier call sites never run in one iteration);
+//     program counter stays wave-uniform.  A wave of empty magnitudes has no window: m^0 = 1;
 //   * a refused request's chains, and the negative chains of a request whose m has no inverse, store zeroes and their status.
 //   products: 1 (to Montgomery form) + 14 (table) + 1 (one) + 2 width * 5 + 1 (leave)        10 per byte of the wave's width
-// The fragments and their signs are SECRET shares.  What does not depend on them: the sequence of products given the widths.  What
-// does: the address of the table row (the digit) and of the base row (the sign).  The widths follow from a fragment's depth in the
-// key tree, which its index kid * n + id + 1 discloses to whoever sees the response.
+// The fragments and their signs are SECRET shares.  Beyond the table row's address, the address of the base row depends on one (the
+// sign).  The widths follow from a fragment's depth in the key tree, which its index kid * n + id + 1 discloses to whoever sees the
+// response.
 // Padding quads (past the launch's chains) run the last chain again on a table of their own and store nothing.
+struct PsignChain : TpaChain {
+  uint32_t used;
+  // (w >> 1: the digit's byte, counted from the row's end; past this chain's width: digit 0)
+  __device__ __forceinline__ uint32_t digit(uint32_t w) const { return (w >> 1) < used ? TpaChain::digit(w) : 0u; }
+};
 __global__ void __launch_bounds__(RSA_BLOCK) k_psign_pow(uint32_t n_here /*chains of this launch*/, uint32_t first /*its first chain*/,
                                                          const uint32_t* __restrict__ order /*[chains] -> fragment*/,
                                                          const uint32_t* __restrict__ frag_req /*[n_frags], below n_reqs*/,
@@ -68,8 +71,8 @@ __global__ void __launch_bounds__(RSA_BLOCK) k_psign_pow(uint32_t n_here /*chain
   const uint32_t* r2p = mt.r2_limbs + (uint64_t)mi * MONT_N + qlane * L;
   const uint32_t* brow = (neg ? inv_limbs : em_limbs) + (uint64_t)req * MONT_N + qlane * L;
   const uint8_t* erow = exps + (uint64_t)frag * exp_len;
-  uint32_t* tab = scratch + (uint64_t)lq * TPA_ENT * MONT_N + qlane * L;      // this lane's limbs of row 0
-  uint32_t n[L], y[L], t[L];          // the register operand of every product is y (R^2 is loaded into it where needed)
+  uint32_t* tab = scratch + (uint64_t)lq * CHAIN_ENT * MONT_N + qlane * L;    // this lane's limbs of row 0
+  uint32_t n[L], t[L];
 #pragma unroll
   for (int k = 0; k < L; ++k) n[k] = mt.n_limbs[(uint64_t)mi * MONT_N + qlane * L + k];
   const uint32_t n0inv = mt.n0inv[mi];
@@ -78,59 +81,8 @@ __global__ void __launch_bounds__(RSA_BLOCK) k_psign_pow(uint32_t n_here /*chain
 #pragma unroll
   for (int off = 32; off >= 4; off >>= 1) wide = max(wide, (uint32_t)__shfl_xor((int)wide, off));
   wide = (uint32_t)__builtin_amdgcn_readfirstlane((int)wide);
-  // wave-uniform program counter
-  enum : int { P_TO_MONT = 0, P_POWERS, P_ONE, P_SQR, P_TABMUL, P_LEAVE };
-  int phase = P_TO_MONT, w = 2 * (int)wide - 1, sq = 0;
-  uint32_t d = 0;                     // P_POWERS: the table row being built
-  for (;;) {
-    // ---- operands: a through LDS, b in registers
-    if (phase == P_TO_MONT) {                       // b * R
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = brow[k]; y[k] = r2p[k]; }
-    } else if (phase == P_POWERS) {                 // b^d = b^(d-1) * b; a = b R stays in LDS, y = the previous power
-    } else if (phase == P_ONE) {                    // Montgomery one = mont(1, R^2)
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = (qlane == 0 && k == 0) ? 1u : 0u; y[k] = r2p[k]; }
-    } else if (phase == P_SQR) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = y[k];
-    } else if (phase == P_TABMUL) {
-      const uint32_t by = (uint32_t)(w >> 1);       // the digit's byte, counted from the row's end; past this chain's width: digit 0
-      const uint32_t dig = by < used ? ((uint32_t)erow[exp_len - 1 - by] >> ((w & 1) * 4)) & 15u : 0u;
-      const uint32_t* row = tab + (uint64_t)dig * MONT_N;
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = row[k];
-    } else {                                        // P_LEAVE: mont(y, 1)
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = (qlane == 0 && k == 0) ? 1u : 0u;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (phase == P_SQR) mont_mul<L, MONT_TPI, true>(t, a_rd, y, n, n0inv, qlane);
-    else mont_mul<L, MONT_TPI, false>(t, a_rd, y, n, n0inv, qlane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // ---- results and next step (scalar control flow)
-    if (phase == P_LEAVE) break;
-#pragma unroll
-    for (int k = 0; k < L; ++k) y[k] = t[k];
-    if (phase == P_TO_MONT) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = t[k]; tab[MONT_N + k] = t[k]; }      // a = b R for the powers
-      d = 2; phase = P_POWERS;
-    } else if (phase == P_POWERS) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) tab[(uint64_t)d * MONT_N + k] = t[k];
-      if (++d == TPA_ENT) phase = P_ONE;
-    } else if (phase == P_ONE) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) tab[k] = t[k];
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");      // own table rows are read back below
-      if (w < 0) phase = P_LEAVE; else { phase = P_SQR; sq = 0; }      // (a wave of empty magnitudes: m^0 = 1)
-    } else if (phase == P_SQR) {
-      if (++sq == 4) phase = P_TABMUL;
-    } else {                                        // P_TABMUL
-      if (--w < 0) phase = P_LEAVE; else { phase = P_SQR; sq = 0; }
-    }
-  }
+  PsignChain pol{{brow, r2p, erow, exp_len}, used};
+  window_chain<L, MONT_TPI>(pol, a_lds, a_rd, tab, r2p, n, n0inv, qlane, 2 * (int)wide, t);
   canonicalize(t, qlane);
   if (!active) return;
   uint32_t* o = out_limbs + (uint64_t)frag * MONT_N + qlane * L;

@@ -155,7 +155,7 @@ int rsas_run(bftkv_gpu_ctx* c, const RsaSignerSet& ks, const RsasOut& o, const u
   if (!dev && ((rc = dev_alloc(c, sb, (size_t)n_ops * nbytes, &d_sig, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_st, false)))) return rc;
   const uint32_t per_launch = std::min(n_ops, RSAS_LAUNCH_SIGS);
   const dim3 crt_grid((per_launch + RSAS_SIGS_PER_BLOCK - 1) / RSAS_SIGS_PER_BLOCK);
-  const size_t limbs_bytes = (size_t)n_ops * RSAS_VALUE_LIMBS * 4, tab_bytes = (size_t)crt_grid.x * QUADS_PER_BLOCK * RSAS_ENT * RSAS_N * 4;
+  const size_t limbs_bytes = (size_t)n_ops * RSAS_VALUE_LIMBS * 4, tab_bytes = (size_t)crt_grid.x * QUADS_PER_BLOCK * CHAIN_ENT * RSAS_N * 4;
   if ((rc = dev_alloc(c, sb, limbs_bytes, &d_c, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_rule, false)) ||
       (rc = dev_alloc(c, sb, tab_bytes, &d_tab, false)) || (rc = dev_alloc(c, sb, limbs_bytes, &d_m2h, true)) ||
       (rc = dev_alloc(c, sb, limbs_bytes, &d_s, false)) || (rc = dev_alloc(c, sb, (size_t)n_ops + 8, &d_fits, false)))

@@ -8,7 +8,7 @@
 //   k_rsas_finish      the status of every signature; a row that is not BFTKV_TH_OK is zeroed
 // The rules: rsa_sign.h and docs/parity.md, "RSA signing (rsa.SignPKCS1v15)".
 #pragma once
-// (kernels.hip, rsa_verify_kernels.hip and tpa_kernels.hip are included before this file by capi.hip)
+// (kernels.hip, rsa_verify_kernels.hip and window_chain.h are included before this file by capi.hip)
 #include "rsa_sign.h"
 
 namespace bftkv {
@@ -26,7 +26,6 @@ struct RsasKeys {
   uint32_t n_keys, pbytes;
 };
 
-constexpr int RSAS_ENT = 16;                                   // rows of a chain's table: b^0 .. b^15
 constexpr int RSAS_SIGS_PER_BLOCK = QUADS_PER_BLOCK / 2;       // two quads per signature
 
 __device__ __forceinline__ uint32_t rsas_key(const uint32_t* __restrict__ key_idx, uint32_t op, uint32_t n_keys) {
@@ -76,18 +75,73 @@ __device__ __forceinline__ void rsas_sub_2n(uint32_t (&x)[L], const uint32_t (&a
 // One signature per PAIR of quads of one wave: the even quad raises c mod p to dp, the odd one c mod q to dq, on the 10 x 4 form
 // (40 limbs of 28 bits, R = 2^1120 > 2^96 p: mont_mul<10, 4>'s ring path; the model's figures: tests/test_rsa_sign_reference.py).
 //   base      c = hi 2^1120 + lo:  mont(hi, R^3) + mont(lo, R^2) = c R mod m, below 4m
-//   chain     k_tpa_pow's: the table b^0 .. b^15 in Montgomery form to global memory, written and re-read by the same lanes, then every
-//             window is 4 squarings and ONE product by the row its digit names, for the set's 2 pbytes windows -- the row of a zero
-//             digit is the Montgomery one, so nothing is skipped and nothing selected
+//   chain     window_chain (window_chain.h, with what depends on a secret and what does not) over the set's 2 pbytes windows
 //   leave     mont(y, 1), canonical and below m: the odd quad's is m2
 //   meet      m2 crosses through the odd quad's LDS slice (one wave: wavefront fences);  z = mont(m2, R^2 mod p);
 //             x = y1 + 2p - z;  u = mont(x, qinv R);  h = mont(u, 1), canonical and below p
-// The odd quad runs the meeting's products too, on operands of its own that nobody reads: the program counter stays wave-uniform and
-// there are two multiplier call sites, as in k_tpa_pow and for its reason (registers).
+// The odd quad runs the meeting's products too, on operands of its own that nobody reads: the program counter stays wave-uniform.
 //   products: 2 (base) + 14 (table) + 1 (one) + 2 pbytes * 5 + 1 (leave) + 3 (meeting)        1,301 per half at 128 bytes
-// p, q, dp, dq and qinv are SECRETS.  What does not depend on them: the sequence of products, which follows from the set's pbytes
-// alone.  What does: the address of the table row (the digit) -- and nothing else.
+// p, q, dp, dq and qinv are SECRETS.  The sequence of products follows from the set's pbytes alone, and the entry and exit products
+// add no address that depends on one: the table row's (the digit) is the only one.
 // Padding pairs (past the launch's signatures) run the last signature again on tables of their own and store nothing.
+struct RsasChain {
+  static constexpr int PRE = 2, POST = 3, L = RSAS_L;
+  const uint32_t (&n)[L];
+  const uint32_t *crow, *r2p, *r3p, *qinvp;         // this lane's limbs of c (low | high), R^2, R^3 and qinv R
+  const uint8_t* erow;
+  uint32_t pbytes;
+  const uint32_t* a_odd;                            // the LDS slice of the pair's odd quad: where m2 crosses
+  uint32_t* m2row;                                  // this lane's limbs of m2 in m2h
+  bool half, active;
+  int qlane;
+  uint32_t keep[L];                                 // the base's high part, then y1
+  __device__ __forceinline__ void pre_load(int step, uint32_t* a_lds, uint32_t (&y)[L]) const {      // hi * R^3, then lo * R^2
+    const uint32_t *r2 = r2p, *r3 = r3p;
+    const uint32_t *src = step == 0 ? crow + RSAS_N : crow, *rr = step == 0 ? r3 : r2;
+#pragma unroll
+    for (int k = 0; k < L; ++k) { a_lds[k] = src[k]; y[k] = rr[k]; }
+  }
+  __device__ __forceinline__ void pre_done(int step, uint32_t (&t)[L]) {
+    if (step == 0) {
+#pragma unroll
+      for (int k = 0; k < L; ++k) keep[k] = t[k];
+    } else {                                        // c R mod m below 4m: canonical, the base of the powers and row 1
+#pragma unroll
+      for (int k = 0; k < L; ++k) t[k] += keep[k];
+      canonicalize<L, RSAS_TPI>(t, qlane);
+    }
+  }
+  __device__ __forceinline__ uint32_t digit(uint32_t w) const { return rsas_digit(erow, pbytes, w); }
+  // y: the power in Montgomery form, kept; t: the power itself, at most m
+  __device__ __forceinline__ void leave_done(uint32_t (&t)[L], const uint32_t (&y)[L], uint32_t* a_lds) {
+#pragma unroll
+    for (int k = 0; k < L; ++k) keep[k] = y[k];
+    canonicalize<L, RSAS_TPI>(t, qlane);
+    reduce_once<L, RSAS_TPI>(t, n, qlane);
+    if (half) {
+#pragma unroll
+      for (int k = 0; k < L; ++k) a_lds[k] = t[k];
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) m2row[k] = t[k];
+      }
+    }
+  }
+  // step 0: a = m2 in the odd quad's slice (written behind the leave), b = R^2;  1: a = x (written behind step 0), b = qinv R;
+  // 2: mont(y, 1).  The members are read ahead of the branches, so that the object is taken apart into registers.
+  __device__ __forceinline__ const uint32_t* post_load(int step) const {
+    const uint32_t *r2 = r2p, *qi = qinvp;
+    return step == 0 ? r2 : step == 1 ? qi : nullptr;
+  }
+  __device__ __forceinline__ const uint32_t* post_slice(int step, const uint32_t* a_own) const { return step == 0 ? a_odd : a_own; }
+  __device__ __forceinline__ void post_done(int step, const uint32_t (&t)[L], uint32_t* a_lds) const {
+    if (step != 0) return;
+    uint32_t x[L];                                  // x = y1 + 2p - m2 R, canonical, below 4p
+    rsas_sub_2n<L>(x, keep, n, t, qlane);
+#pragma unroll
+    for (int k = 0; k < L; ++k) a_lds[k] = x[k];
+  }
+};
 __global__ void __launch_bounds__(RSA_BLOCK) k_rsas_crt(uint32_t n_here /*signatures of this launch*/, uint32_t first /*its first signature*/,
                                                         const uint32_t* __restrict__ key_idx, RsasKeys ks,
                                                         const uint32_t* __restrict__ c_limbs /*[n_ops][80]*/,
@@ -108,105 +162,14 @@ __global__ void __launch_bounds__(RSA_BLOCK) k_rsas_crt(uint32_t n_here /*signat
   const uint32_t* r2p = ks.r2 + prow;
   const uint32_t* crow = c_limbs + (uint64_t)op * RSAS_VALUE_LIMBS + qlane * L;
   const uint8_t* erow = ks.d + ((uint64_t)key * 2 + half) * ks.pbytes;
-  uint32_t* tab = scratch + (uint64_t)lq * RSAS_ENT * RSAS_N + qlane * L;    // this lane's limbs of row 0
-  uint32_t n[L], y[L], t[L], keep[L];     // the register operand of every product is y; keep: the base's high part, then y1
+  uint32_t* tab = scratch + (uint64_t)lq * CHAIN_ENT * RSAS_N + qlane * L;   // this lane's limbs of row 0
+  uint32_t n[L], t[L];
 #pragma unroll
   for (int k = 0; k < L; ++k) n[k] = ks.mod[prow + k];
   const uint32_t n0inv = ks.n0inv[key * 2 + half];
-  const uint32_t pbytes = ks.pbytes;
-  // wave-uniform program counter
-  enum : int { P_HI = 0, P_LO, P_POWERS, P_ONE, P_SQR, P_TABMUL, P_LEAVE, P_M2P, P_QINV, P_OUT };
-  int phase = P_HI, w = 2 * (int)pbytes - 1, sq = 0;
-  uint32_t d = 0;                         // P_POWERS: the table row being built
-  for (;;) {
-    // ---- operands: a through LDS, b in registers
-    if (phase == P_HI || phase == P_LO) {
-      const uint32_t* src = phase == P_HI ? crow + RSAS_N : crow;
-      const uint32_t* rr = phase == P_HI ? ks.r3 + prow : r2p;
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = src[k]; y[k] = rr[k]; }
-    } else if (phase == P_POWERS) {                 // b^d = b^(d-1) * b; a = b R stays in LDS, y = the previous power
-    } else if (phase == P_ONE) {                    // Montgomery one = mont(1, R^2)
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = (qlane == 0 && k == 0) ? 1u : 0u; y[k] = r2p[k]; }
-    } else if (phase == P_SQR) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = y[k];
-    } else if (phase == P_TABMUL) {
-      const uint32_t* row = tab + (uint64_t)rsas_digit(erow, pbytes, (uint32_t)w) * RSAS_N;
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = row[k];
-    } else if (phase == P_M2P) {                    // a = m2 in the odd quad's slice (written behind P_LEAVE), b = R^2
-#pragma unroll
-      for (int k = 0; k < L; ++k) y[k] = r2p[k];
-    } else if (phase == P_QINV) {                   // a = x (written behind P_M2P), b = qinv R
-#pragma unroll
-      for (int k = 0; k < L; ++k) y[k] = ks.qinv_r[(uint64_t)key * RSAS_N + qlane * L + k];
-    } else {                                        // P_LEAVE, P_OUT: mont(y, 1)
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = (qlane == 0 && k == 0) ? 1u : 0u;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const uint32_t* a_rd = phase == P_M2P ? a_odd : a_own;
-    if (phase == P_SQR) mont_mul<L, RSAS_TPI, true>(t, a_rd, y, n, n0inv, qlane);
-    else mont_mul<L, RSAS_TPI, false>(t, a_rd, y, n, n0inv, qlane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // ---- results and next step (scalar control flow)
-    if (phase == P_OUT) break;
-    if (phase == P_HI) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) keep[k] = t[k];
-      phase = P_LO;
-    } else if (phase == P_LO) {                     // c R mod m below 4m: canonical, the base of the powers and row 1
-#pragma unroll
-      for (int k = 0; k < L; ++k) t[k] += keep[k];
-      canonicalize<L, RSAS_TPI>(t, qlane);
-#pragma unroll
-      for (int k = 0; k < L; ++k) { y[k] = t[k]; a_lds[k] = t[k]; tab[RSAS_N + k] = t[k]; }
-      d = 2; phase = P_POWERS;
-    } else if (phase == P_POWERS) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) { y[k] = t[k]; tab[(uint64_t)d * RSAS_N + k] = t[k]; }
-      if (++d == RSAS_ENT) phase = P_ONE;
-    } else if (phase == P_ONE) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) { y[k] = t[k]; tab[k] = t[k]; }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");      // own table rows are read back below
-      phase = P_SQR; sq = 0;
-    } else if (phase == P_SQR) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) y[k] = t[k];
-      if (++sq == 4) phase = P_TABMUL;
-    } else if (phase == P_TABMUL) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) y[k] = t[k];
-      if (--w < 0) phase = P_LEAVE; else { phase = P_SQR; sq = 0; }
-    } else if (phase == P_LEAVE) {                  // y: the power in Montgomery form, kept; t: the power itself, at most m
-#pragma unroll
-      for (int k = 0; k < L; ++k) keep[k] = y[k];
-      canonicalize<L, RSAS_TPI>(t, qlane);
-      reduce_once<L, RSAS_TPI>(t, n, qlane);
-      if (half) {
-#pragma unroll
-        for (int k = 0; k < L; ++k) a_lds[k] = t[k];
-        if (active) {
-#pragma unroll
-          for (int k = 0; k < L; ++k) m2h[(uint64_t)op * RSAS_VALUE_LIMBS + qlane * L + k] = t[k];
-        }
-      }
-      phase = P_M2P;
-    } else if (phase == P_M2P) {                    // x = y1 + 2p - m2 R, canonical, below 4p
-      uint32_t x[L];
-      rsas_sub_2n<L>(x, keep, n, t, qlane);
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = x[k];
-      phase = P_QINV;
-    } else {                                        // P_QINV
-#pragma unroll
-      for (int k = 0; k < L; ++k) y[k] = t[k];
-      phase = P_OUT;
-    }
-  }
+  RsasChain pol{n, crow, r2p, ks.r3 + prow, ks.qinv_r + (uint64_t)key * RSAS_N + qlane * L, erow, ks.pbytes, a_odd,
+                m2h + (uint64_t)op * RSAS_VALUE_LIMBS + qlane * L, half != 0u, active, qlane};
+  window_chain<L, RSAS_TPI>(pol, a_lds, a_own, tab, r2p, n, n0inv, qlane, 2 * (int)ks.pbytes, t);
   canonicalize<L, RSAS_TPI>(t, qlane);
   reduce_once<L, RSAS_TPI>(t, n, qlane);
   if (!active || half) return;

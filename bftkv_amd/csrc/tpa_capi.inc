@@ -56,7 +56,7 @@ int tpa_run(bftkv_gpu_ctx* c, TpaMode mode, const TpaOut& o, const uint8_t* base
   const uint32_t per_launch = std::min(chains, TPA_LAUNCH_CHAINS);
   const size_t tab_quads = (size_t)quad_grid(per_launch).x * QUADS_PER_BLOCK;
   if ((rc = dev_alloc(c, sb, (size_t)chains * MONT_N * 4, &d_base, false)) || (rc = dev_alloc(c, sb, (size_t)chains * MONT_N * 4, &d_out, false)) ||
-      (rc = dev_alloc(c, sb, tab_quads * TPA_ENT * MONT_N * 4, &d_tab, false)) || (rc = dev_alloc(c, sb, (size_t)chains * nbytes, &d_bytes, false)))
+      (rc = dev_alloc(c, sb, tab_quads * CHAIN_ENT * MONT_N * 4, &d_tab, false)) || (rc = dev_alloc(c, sb, (size_t)chains * nbytes, &d_bytes, false)))
     return rc;
   const dim3 limb_grid((uint32_t)(((size_t)n_ops * MONT_N + 255) / 256));
   hipLaunchKernelGGL(k_tpa_bytes_to_limbs, limb_grid, dim3(256), 0, s, (const uint8_t*)d_b0, nbytes, (const uint32_t*)nullptr, n_ops, (uint32_t*)d_base);

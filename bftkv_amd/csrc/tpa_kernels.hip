@@ -5,7 +5,7 @@
 //   k_tpa_finish           keySched (HKDF-SHA256 over Ki.Bytes()) and the MAC (HMAC-SHA256 over Xi | Bi.Bytes())
 // The rules: docs/parity.md, "Password authentication (crypto/auth)".
 #pragma once
-// (kernels.hip and threshold_kernels.hip are included before this file by capi.hip)
+// (kernels.hip, threshold_kernels.hip and window_chain.h are included before this file by capi.hip)
 
 namespace bftkv {
 
@@ -26,15 +26,23 @@ __global__ void k_tpa_bytes_to_limbs(const uint8_t* __restrict__ src, uint32_t n
 // whose exponent and modulus it takes -- makeBi's two powers v^b and Xi^b are two chains that share b, in different quads, so the
 // registers of a quad are those of one chain.
 //
-// Fixed 4-bit windows over all 2 * exp_len digits of the exponent row, most significant first: the table b^0 .. b^15 (Montgomery form,
-// b^0 = R mod p) goes to global memory, written and re-read by the same lanes (4.75 KB per quad of the launch), then every window is 4
-// squarings and ONE multiplication by the row its digit names -- the row of a zero digit is the Montgomery one, so nothing is skipped
-// and nothing selected: the sequence of products is a function of exp_len, the same in every lane, whatever the exponents (y of makeYi
-// and b of makeBi are secrets).  The ADDRESS of the table row does depend on the digit.
+// The chain is window_chain (window_chain.h, with what depends on a secret and what does not) over all 2 * exp_len digits of the
+// exponent row: the schedule depends on exp_len alone, whatever the exponents (y of makeYi and b of makeBi are secrets).  The table
+// is 4.75 KB per quad of the launch.
 //   products: 1 (to Montgomery form) + 14 (table) + 1 (one) + 2 exp_len * 5 + 1 (leave)        2,577 at 256 exponent bytes
-// One loop with two multiplier call sites (general and squaring), as k_multiexp and for its reason (registers).
 // Padding quads (past the launch's chains) run the last chain again on a table of their own and store no result.
-constexpr int TPA_ENT = 16;
+struct TpaChain {
+  static constexpr int PRE = 1, POST = 0;
+  const uint32_t *brow, *r2p;         // this lane's limbs of the base and of R^2
+  const uint8_t* erow;
+  uint32_t exp_len;
+  __device__ __forceinline__ void pre_load(int, uint32_t* a_lds, uint32_t (&y)[MONT_L]) const {      // b * R
+#pragma unroll
+    for (int k = 0; k < MONT_L; ++k) { a_lds[k] = brow[k]; y[k] = r2p[k]; }
+  }
+  __device__ __forceinline__ void pre_done(int, uint32_t (&)[MONT_L]) const {}
+  __device__ __forceinline__ uint32_t digit(uint32_t w) const { return ((uint32_t)erow[exp_len - 1 - (w >> 1)] >> ((w & 1) * 4)) & 15u; }
+};
 __global__ void __launch_bounds__(RSA_BLOCK) k_tpa_pow(uint32_t n_here /*chains of this launch*/, uint32_t first /*its first chain*/, uint32_t n_ops,
                                                        const uint32_t* __restrict__ base_limbs /*[chains][76]*/,
                                                        const uint8_t* __restrict__ exps /*[n_ops][exp_len] big-endian*/, uint32_t exp_len,
@@ -55,63 +63,13 @@ __global__ void __launch_bounds__(RSA_BLOCK) k_tpa_pow(uint32_t n_here /*chains 
   const uint32_t* r2p = mt.r2_limbs + (uint64_t)mi * MONT_N + qlane * L;
   const uint32_t* brow = base_limbs + (uint64_t)chain * MONT_N + qlane * L;
   const uint8_t* erow = exps + (uint64_t)op * exp_len;
-  uint32_t* tab = scratch + (uint64_t)lq * TPA_ENT * MONT_N + qlane * L;      // this lane's limbs of row 0
-  uint32_t n[L], y[L], t[L];          // the register operand of every product is y (R^2 is loaded into it where needed)
+  uint32_t* tab = scratch + (uint64_t)lq * CHAIN_ENT * MONT_N + qlane * L;    // this lane's limbs of row 0
+  uint32_t n[L], t[L];
 #pragma unroll
   for (int k = 0; k < L; ++k) n[k] = mt.n_limbs[(uint64_t)mi * MONT_N + qlane * L + k];
   const uint32_t n0inv = mt.n0inv[mi];
-  // wave-uniform program counter
-  enum : int { P_TO_MONT = 0, P_POWERS, P_ONE, P_SQR, P_TABMUL, P_LEAVE };
-  int phase = P_TO_MONT, w = 2 * (int)exp_len - 1, sq = 0;
-  uint32_t d = 0;                     // P_POWERS: the table row being built
-  for (;;) {
-    // ---- operands: a through LDS, b in registers
-    if (phase == P_TO_MONT) {                       // b * R
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = brow[k]; y[k] = r2p[k]; }
-    } else if (phase == P_POWERS) {                 // b^d = b^(d-1) * b; a = b R stays in LDS, y = the previous power
-    } else if (phase == P_ONE) {                    // Montgomery one = mont(1, R^2)
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = (qlane == 0 && k == 0) ? 1u : 0u; y[k] = r2p[k]; }
-    } else if (phase == P_SQR) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = y[k];
-    } else if (phase == P_TABMUL) {
-      const uint32_t dig = ((uint32_t)erow[exp_len - 1 - (uint32_t)(w >> 1)] >> ((w & 1) * 4)) & 15u;
-      const uint32_t* row = tab + (uint64_t)dig * MONT_N;
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = row[k];
-    } else {                                        // P_LEAVE: mont(y, 1)
-#pragma unroll
-      for (int k = 0; k < L; ++k) a_lds[k] = (qlane == 0 && k == 0) ? 1u : 0u;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (phase == P_SQR) mont_mul<L, MONT_TPI, true>(t, a_rd, y, n, n0inv, qlane);
-    else mont_mul<L, MONT_TPI, false>(t, a_rd, y, n, n0inv, qlane);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // ---- results and next step (scalar control flow)
-    if (phase == P_LEAVE) break;
-#pragma unroll
-    for (int k = 0; k < L; ++k) y[k] = t[k];
-    if (phase == P_TO_MONT) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) { a_lds[k] = t[k]; tab[MONT_N + k] = t[k]; }      // a = b R for the powers
-      d = 2; phase = P_POWERS;
-    } else if (phase == P_POWERS) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) tab[(uint64_t)d * MONT_N + k] = t[k];
-      if (++d == TPA_ENT) phase = P_ONE;
-    } else if (phase == P_ONE) {
-#pragma unroll
-      for (int k = 0; k < L; ++k) tab[k] = t[k];
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");      // own table rows are read back below
-      phase = P_SQR; sq = 0;
-    } else if (phase == P_SQR) {
-      if (++sq == 4) phase = P_TABMUL;
-    } else {                                        // P_TABMUL
-      if (--w < 0) phase = P_LEAVE; else { phase = P_SQR; sq = 0; }
-    }
-  }
+  TpaChain pol{brow, r2p, erow, exp_len};
+  window_chain<L, MONT_TPI>(pol, a_lds, a_rd, tab, r2p, n, n0inv, qlane, 2 * (int)exp_len, t);
   canonicalize(t, qlane);
   if (active) store_mod_result(out_limbs + (uint64_t)chain * MONT_N + qlane * L, t, n, qlane);
 }

@@ -199,6 +199,17 @@ def test_sixteen_widths_in_one_wave(gpu_ctx, caller_order_ctx):
     assert_rows(out, st, [(s, v.to_bytes(128, "big")) for s, v in K.expected(ci)], "e513_n128 as submitted")
 
 
+def test_a_wave_of_empty_magnitudes(gpu_ctx):
+    """every chain of the call's one wave has exp_used 0, under sign bytes of both kinds: no window at all, from the table straight to
+    the leave -- m^0 = 1 in every row"""
+    reqs = [(K.kat()["n"], K.tree_t())]
+    frags = [(0, 1, 0, 0), (0, 0, 0, 0), (0, 0xFF, 0, 0)]
+    out, st = sign_call(gpu_ctx, reqs, frags, 256, 2)
+    want = want_rows(reqs, frags, 256)
+    assert want == [(R.OK, (1).to_bytes(256, "big"))] * 3
+    assert_rows(out, st, want)
+
+
 def test_more_chains_than_one_launch_takes(gpu_ctx):
     n = TPA_LAUNCH_CHAINS + 17
     mod = K.moduli()["odd520"]

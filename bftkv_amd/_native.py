@@ -41,7 +41,7 @@ EXPORTS = [
     "bftkv_gpu_comm_unique_id", "bftkv_gpu_comm_init", "bftkv_gpu_allgather_verdicts", "bftkv_gpu_sss_distribute", "bftkv_gpu_modinv",
     "bftkv_gpu_batcher_create", "bftkv_gpu_batcher_destroy", "bftkv_gpu_batcher_collective_verify",
     "bftkv_gpu_batcher_signature_verify", "bftkv_gpu_batcher_stats", "bftkv_gpu_set_dsa_window_bits", "bftkv_gpu_dsa_window_bits", "bftkv_gpu_set_dsa_table_budget", "bftkv_gpu_dsa_table_bytes", "bftkv_gpu_collective_verify_segments", "bftkv_gpu_message_verify", "bftkv_gpu_batcher_message_verify",
-    "bftkv_gpu_modexp_ops", "bftkv_gpu_allgather_errs_dev", "bftkv_gpu_set_early_exit", "bftkv_gpu_last_sclk_mhz", "bftkv_gpu_modmul_product_dev", "bftkv_gpu_lagrange_combine_dev",
+    "bftkv_gpu_modexp_ops", "bftkv_gpu_allgather_errs_dev", "bftkv_gpu_set_early_exit", "bftkv_gpu_last_sclk_mhz", "bftkv_gpu_last_plan_report", "bftkv_gpu_modmul_product_dev", "bftkv_gpu_lagrange_combine_dev",
     "bftkv_gpu_dsa_calculate_r_dev", "bftkv_gpu_sss_distribute_dev", "bftkv_gpu_modinv_dev",
     "bftkv_gpu_ctx_fork", "bftkv_gpu_batcher_create_lanes", "bftkv_gpu_batcher_times", "bftkv_gpu_comm_library", "bftkv_gpu_comm_selftest",
     "bftkv_gpu_collective_verify_small", "bftkv_gpu_signature_verify_small", "bftkv_gpu_set_hash_policy", "bftkv_gpu_signers_fenced",
@@ -141,6 +141,7 @@ def load_library() -> C.CDLL:
     lib.bftkv_gpu_set_host_pipeline.argtypes = [vp, u32]
     lib.bftkv_gpu_host_pipeline_trace.argtypes = [vp, C.POINTER(C.c_float), u32, C.POINTER(u32)]
     lib.bftkv_gpu_last_sclk_mhz.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.bftkv_gpu_last_plan_report.argtypes = [vp, C.POINTER(u32), u32, C.POINTER(u32)]
     lib.bftkv_gpu_modexp_ops.argtypes = lib.bftkv_gpu_modexp.argtypes
     lib.bftkv_gpu_allgather_errs_dev.argtypes = [vp, u8p, u32, u32, u8p]
     lib.bftkv_gpu_modmul_product_dev.argtypes = lib.bftkv_gpu_modmul_product.argtypes
@@ -471,6 +472,21 @@ class Context:
         v = C.c_float(0)
         self._check(self.lib.bftkv_gpu_last_sclk_mhz(self.h, C.byref(v)), "last_sclk_mhz")
         return float(v.value)
+
+    PLAN_REPORT_SLOTS = (
+        "words", "phase2_bound", "walk_fill", "mid_other", "mid_text",
+        "wide1", "compare1", "compare1_3072", "compare1_4096", "dsa_mul1", "dsa_split1", "dsa_modexp1_4", "dsa_modexp1_8",
+        "modexp2", "wide2", "modexp2_3072", "modexp2_4096", "compare2", "compare2_3072", "compare2_4096",
+        "dsa_inv2_batched", "dsa_inv2", "dsa_mul2", "dsa_split2", "dsa_modexp2_4", "dsa_modexp2_8", "total")
+
+    def last_plan_report(self):
+        """Blocks per launch (0: not launched) of what the last resident big verify call enqueued behind its modexp
+        (csrc/plan_report.h); raises NativeError when the last call was of another kind."""
+        n = C.c_uint32(0)
+        out = (C.c_uint32 * 64)()
+        self._check(self.lib.bftkv_gpu_last_plan_report(self.h, out, 64, C.byref(n)), "last_plan_report")
+        assert n.value == len(self.PLAN_REPORT_SLOTS), n.value
+        return {k: int(out[i]) for i, k in enumerate(self.PLAN_REPORT_SLOTS)}
 
     def last_timing(self):
         ms = (C.c_float * 8)()

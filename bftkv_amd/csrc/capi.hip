@@ -259,7 +259,9 @@ struct bftkv_gpu_ctx {
   uint32_t* d_mail = nullptr;
   uint32_t last_total = 0, last_rsa = 0, last_items = 0;
   bool last_total_on_dev = false;      // the last call was sized by an upper bound: its packet count is c->total[0] on the device
-  hipEvent_t ev[10] = {};  // 0 start, 1 parsed, 2 modexp done, 3 compare + DSA done, 4 end, 5 hash start, 6 hash done, 7 DSA inverses done, 8 compare done,
+  bool have_plan_report = false;       // the last call was a resident big call under a plan: what it launched (bftkv_gpu_last_plan_report)
+  uint32_t last_plan_report[plan_report::N_SLOTS] = {};
+  hipEvent_t ev[10] = {};  // 0 start, 1 parsed, 2 modexp done (a big call sized by the plan's report: without its pass over long values), 3 compare + DSA done, 4 end, 5 hash start, 6 hash done, 7 DSA inverses done, 8 compare done,
                            // 9 modexp about to start (behind the turnstile)
   hipEvent_t ev_turn = nullptr;   // this context's ticket in the device's modexp turnstile (below)
   bool have_timing = false;
@@ -609,10 +611,12 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   constexpr size_t CHUNK_ARENA_MIN = 64u << 10;
   if (!c->chunk_ctr.p) { HIPCHK(c, c->chunk_ctr.ensure(16)); HIPCHK(c, hipMemsetAsync(c->chunk_ctr.p, 0, 16, c->stream)); }
   HIPCHK(c, c->chunk_arena.ensure(CHUNK_ARENA_MIN + (staged_cap ? 2 * (size_t)ss_len : 0)));
-  HIPCHK(c, c->pk_count.ensure(96));   // [0..3] work-list lengths, [4] some signature uses a hash other than SHA-256,
+  HIPCHK(c, c->pk_count.ensure(sizeof(uint32_t) * PK_COUNT_WORDS));
+                                       // [0..3] work-list lengths, [4] some signature uses a hash other than SHA-256,
                                        // [5] some RSA value is too long for the 29-bit form (SIGF_WIDE_VALUE),
                                        // [8..11] lengths after phase 1 (phase 2's start), [12..15] zeros (phase 1's start),
-                                       // [16..19] two uint64: clock stamps of k_rsa_modexp (bftkv_gpu_last_sclk_mhz)
+                                       // [16..19] two uint64: clock stamps of k_rsa_modexp (bftkv_gpu_last_sclk_mhz),
+                                       // [20..23] DSA class counts (k_dsa_split), [24] k_plan<1>'s ticket (PK_PLAN_TICKET)
   if (plan_q) HIPCHK(c, c->plan_cut.ensure(sizeof(uint32_t) * (size_t)n_items + 16));
   TextDev txt{nullptr, nullptr, nullptr, nullptr};
   if (!d_mid_in) {      // (a midstate-only call cannot hash text-mode signatures: their items come back marked for the ordinary path)
@@ -628,7 +632,7 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   HIPCHK(c, join(sh, 0));
   HIPCHK(c, rec(5, sh));
   if (!upload_tbs && !d_mid_in)
-    hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + 63) / 64), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
+    hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + MID_BLOCK - 1) / MID_BLOCK), dim3(MID_BLOCK), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
   hipLaunchKernelGGL(k_walk<false>, dim3(n_items), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
                      (const uint32_t*)nullptr, (SigRec*)nullptr, c->item_flags.as<uint8_t>(), c->walk_scratch.as<WalkEnt>(), walk_cap,
                      c->chunk_ctr.as<uint32_t>());
@@ -636,7 +640,7 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   if (c->h_mail && !staged_cap) __atomic_store_n(&c->h_mail[0], MAIL_EMPTY, __ATOMIC_RELEASE);
   hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, c->counts.as<uint32_t>(), n_items, c->base.as<uint32_t>(),
                      c->total.as<uint32_t>(), staged_cap ? (uint32_t*)nullptr : c->d_mail, c->pk_count.as<uint32_t>(), c->hash_mask.as<uint32_t>(),
-                     staged_cap, c->chunk_ctr.as<uint32_t>());
+                     staged_cap, c->chunk_ctr.as<uint32_t>(), staged_cap ? (const uint8_t*)nullptr : c->item_flags.as<uint8_t>(), walk_cap);
   uint32_t total = staged_cap ? staged_cap : MAIL_EMPTY;      // staged: the upper bound; the kernels read the count from c->total
   const uint32_t* const n_recs_dev = staged_cap ? c->total.as<uint32_t>() : nullptr;
   if (c->h_mail && !staged_cap) {
@@ -649,7 +653,9 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
       __builtin_ia32_pause();
     }
   }
-  uint32_t chunk_units = (c->h_mail && !staged_cap && total != MAIL_EMPTY) ? c->h_mail[2] : 0u;
+  const bool scan_mailed = c->h_mail && !staged_cap && total != MAIL_EMPTY;
+  uint32_t chunk_units = scan_mailed ? c->h_mail[2] : 0u;
+  const uint32_t overflow_items = scan_mailed ? c->h_mail[plan_report::MAIL_OVERFLOW] : 0u;      // (written ahead of the packet count)
   if (total == MAIL_EMPTY) {
     HIPCHK(c, hipMemcpyAsync(&total, c->total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(&chunk_units, c->chunk_ctr.as<uint32_t>() + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -673,9 +679,28 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   HIPCHK(c, c->dsa_list.ensure(sizeof(uint32_t) * tr));
   if (c->have_dsa_keys) HIPCHK(c, c->dsa_u.ensure(sizeof(uint32_t) * DSA_U_WORDS * tr));
   if (c->have_dsa3072 && c->have_dsa2048) HIPCHK(c, c->dsa_idx.ensure(sizeof(uint32_t) * 4 * (size_t)tr + 16));      // k_dsa_split: two class lists per phase
-  // fill pass only for items whose event list overflowed the scratch (a no-op grid otherwise)
-  hipLaunchKernelGGL(k_walk<true>, dim3(n_items), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
-                     c->base.as<uint32_t>(), c->recs.as<SigRec>(), c->item_flags.as<uint8_t>(), (WalkEnt*)nullptr, walk_cap, (uint32_t*)nullptr);
+  // A resident big call under a plan sizes what it enqueues from here on by what the device reports (plan_report.h): the scan's
+  // overflow count now, k_plan<1>'s words once the machine-filling modexp is in the queue.  BFTKV_PLAN_REPORT=0: the words are
+  // ignored, and the call is enqueued as every other call is -- grids over `total`, in the order below.
+  static const bool report_on = []{ const char* e = getenv("BFTKV_PLAN_REPORT"); return !(e && atoi(e) == 0); }();
+  const bool big = staged_cap ? (ev_input != nullptr && ss_len / 320 >= TURNSTILE_MIN_PACKETS) : total >= TURNSTILE_MIN_PACKETS;
+  const bool report_path = total && plan_q && big && c->h_mail && !staged_cap && !upload_tbs && !d_mid_in;
+  const bool by_report = report_path && report_on;
+  plan_report::Input rin;
+  rin.total = total; rin.n_items = n_items; rin.enabled = by_report;
+  rin.overflow_arrived = scan_mailed; rin.overflow_items = overflow_items;
+  rin.wide_form = BFTKV_RSA_FORM == 29; rin.have_rsa3072 = c->have_rsa3072; rin.have_rsa4096 = c->have_rsa4096; rin.have_dsa2048 = c->have_dsa2048; rin.have_dsa3072 = c->have_dsa3072;
+  plan_report::Geometry geo;      // (the kernels' own constants: a build with another block size sizes by that)
+  geo.modexp4 = MODEXP_BLOCK / MONT_TPI; geo.modexp8 = MODEXP_BLOCK / MONT_TPI_BIG; geo.compare = 256 / CMP_LANES; geo.dsa_mul = 64;
+  geo.dsa_split = 256; geo.dsa4 = QUADS_PER_BLOCK; geo.dsa8 = RSA_BLOCK / MONT_TPI_BIG; geo.inv_tile = INV_TILE; geo.mid_items = 64;
+  geo.n_hashes = N_HASHES;
+  plan_report::Decision dec = plan_report::decide(rin, geo);
+  c->have_plan_report = false;
+  // fill pass only for items whose event list overflowed the scratch (a no-op grid otherwise; not launched when the scan
+  // reported that there are none)
+  if (dec.walk_fill)
+    hipLaunchKernelGGL(k_walk<true>, dim3(n_items), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
+                       c->base.as<uint32_t>(), c->recs.as<SigRec>(), c->item_flags.as<uint8_t>(), (WalkEnt*)nullptr, walk_cap, (uint32_t*)nullptr);
   if (total) {
     ParseArgs pa;
     pa.sig_blob = d_ss; pa.sig_off = d_ss_off; pa.rec_base = c->base.as<uint32_t>(); pa.counts = c->counts.as<uint32_t>(); pa.n_items = n_items;
@@ -703,8 +728,11 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     int min_suff = 0;
     for (int i = 0; i < plan_q->n_qcs; ++i) if (plan_q->suff[i] > 0 && (min_suff == 0 || plan_q->suff[i] < min_suff)) min_suff = plan_q->suff[i];
     pl.margin = 1u + (uint32_t)min_suff / 64u;
-    pl.mail = c->d_mail ? c->d_mail + 3 : nullptr;
-    if (c->h_mail) __atomic_store_n(&c->h_mail[3], 0u, __ATOMIC_RELEASE);
+    pl.mail = c->d_mail ? c->d_mail + plan_report::MAIL_PLAN_FLAGS : nullptr;
+    if (c->h_mail) {
+      __atomic_store_n(&c->h_mail[plan_report::MAIL_PLAN_FLAGS], 0u, __ATOMIC_RELEASE);
+      for (int k = 0; k < plan_report::N_LISTS; ++k) __atomic_store_n(&c->h_mail[plan_report::MAIL_LEN0 + k], 0u, __ATOMIC_RELEASE);
+    }
     hipLaunchKernelGGL(k_plan<1>, dim3((n_items + PLAN_ITEMS - 1) / PLAN_ITEMS), dim3(PLAN_BLOCK), 0, s, pl, c->kt, *plan_q);
   }
   const bool dsa_side = total && c->have_dsa_keys;
@@ -716,25 +744,25 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   const size_t n_slots = c->root ? c->n_dsa_slots : c->dsa_comb_slot.size();
   const uint32_t inv_batch_min = c->dsa_inv_mode == 1 || n_slots > (c->dsa_inv_mode == 2 ? (size_t)INV_MAX_SLOTS : 256) ? 0xFFFFFFFFu
                                  : c->dsa_inv_mode == 2 ? 0u : (uint32_t)std::max<size_t>(4096, 64 * n_slots);
-  auto launch_dsa_inv = [&](hipStream_t st, const uint32_t* start) {
+  auto launch_dsa_inv = [&](hipStream_t st, const uint32_t* start, uint32_t bound /* of the entries behind `start` */) {
     if (inv_batch_min != 0xFFFFFFFFu)
-      hipLaunchKernelGGL(k_dsa_inv_batched, dim3((total + INV_TILE - 1) / INV_TILE), dim3(INV_BLOCK), 0, st, d_ss, c->recs.as<SigRec>(),
+      hipLaunchKernelGGL(k_dsa_inv_batched, dim3((bound + INV_TILE - 1) / INV_TILE), dim3(INV_BLOCK), 0, st, d_ss, c->recs.as<SigRec>(),
                          c->dsa_list.as<uint32_t>(), c->pk_count.as<uint32_t>(), start, c->kt, c->dsa_u.as<uint32_t>(), inv_batch_min);
     if (inv_batch_min != 0u)
-      hipLaunchKernelGGL(k_dsa_inv, dim3((total + 63) / 64), dim3(64), 0, st, d_ss, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(),
+      hipLaunchKernelGGL(k_dsa_inv, dim3((bound + 63) / 64), dim3(64), 0, st, d_ss, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(),
                          c->pk_count.as<uint32_t>(), start, c->kt, c->dsa_u.as<uint32_t>(), inv_batch_min);
   };
   if (total && c->have_dsa_keys) {
     HIPCHK(c, hipStreamWaitEvent(c->stream_d, c->ev[1], 0));
-    launch_dsa_inv(c->stream_d, start0);
+    launch_dsa_inv(c->stream_d, start0, total);
     HIPCHK(c, hipEventRecord(c->ev[7], c->stream_d));
   }
   auto hash_stream_work = [&]() -> int {
   // hash stream: digests need the parsed records
     HIPCHK(c, join(sh, 1));
     if (total) {
-      // other hashes: a no-op grid unless some signature asked for them
-      if (!d_mid_in) {
+      // other hashes: a no-op grid unless some signature asked for them (not launched when the plan reported that none did)
+      if (!d_mid_in && dec.mid_other) {
         hipLaunchKernelGGL(k_hash_mid_other, dim3((n_items + 63) / 64, N_HASHES - 1), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items,
                            c->hash_mask.as<uint32_t>(), c->mid.as<uint32_t>(), c->mid64.as<uint64_t>());
         hipLaunchKernelGGL(k_hash_mid_text, dim3((n_items + 63) / 64, N_HASHES), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items, c->hash_mask.as<uint32_t>(), txt);
@@ -746,7 +774,8 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     HIPCHK(c, rec(6, sh));
     return 0;
   };
-  if (!upload_tbs) { int hrc = hash_stream_work(); if (hrc) return hrc; }
+  // (by the report: behind the wait for the plan's words below -- this work waits for the plan on the device anyway)
+  if (!upload_tbs && !by_report) { int hrc = hash_stream_work(); if (hrc) return hrc; }
   // main stream: modular exponentiations (status bytes are only written by the hash stream meanwhile)
   const dim3 qg((total + MODEXP_BLOCK / MONT_TPI - 1) / (MODEXP_BLOCK / MONT_TPI));
   const dim3 qg8((total + MODEXP_BLOCK / MONT_TPI_BIG - 1) / (MODEXP_BLOCK / MONT_TPI_BIG));   // 8 lanes per number
@@ -754,56 +783,70 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   // eight lanes: 0.68x the instructions per wave, and such a call lasts as long as ONE wave's chain of 18 products.
   static const bool wide8_off = getenv("BFTKV_NO_WIDE8") != nullptr;
   const bool wide8 = staged_cap != 0 && ss_len / 256 <= 8192 && !wide8_off;
-  auto launch_modexp = [&](const uint32_t* start) {
-    if (wide8)
-      hipLaunchKernelGGL((k_rsa_modexp<10, MONT_TPI_BIG>), qg8, dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
-    else {
+  struct ModexpGrids { uint32_t main, wide, m3072, m4096; };      // blocks per launch, 0: not launched
+  const ModexpGrids mg_total{wide8 ? qg8.x : qg.x, qg.x, c->have_rsa3072 ? qg8.x : 0u, c->have_rsa4096 ? qg8.x : 0u};
+  auto launch_modexp = [&](const uint32_t* start, const ModexpGrids& mg) {
+    if (wide8) {
+      if (mg.main)
+        hipLaunchKernelGGL((k_rsa_modexp<10, MONT_TPI_BIG>), dim3(mg.main), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
+    } else {
 #if BFTKV_RSA_FORM == 29
       // 18 x 4 limbs of 29 bits (2 x 64 x 72 x 4 B of LDS per block), and right behind it the 19 x 4 form of 28 bits for the
       // values too long for 72 limbs (262 .. 266 bytes; k_parse_body flags them and raises cnt_p[5]): normally a grid of
       // blocks that read one word and return
-      hipLaunchKernelGGL((k_rsa_modexp<RSA29_L, MONT_TPI, RSA29_W>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16), (const uint32_t*)(cnt_p + 5));
-      hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI, MONT_W, true>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr, (const uint32_t*)(cnt_p + 5));
+      if (mg.main)
+        hipLaunchKernelGGL((k_rsa_modexp<RSA29_L, MONT_TPI, RSA29_W>), dim3(mg.main), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16), (const uint32_t*)(cnt_p + 5));
+      if (mg.wide)
+        hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI, MONT_W, true>), dim3(mg.wide), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr, (const uint32_t*)(cnt_p + 5));
 #else
-      hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI>), qg, dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
+      if (mg.main)
+        hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI>), dim3(mg.main), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
 #endif
     }
     // larger moduli: only when the keyring holds such keys (blocks beyond the queued count exit at once)
-    if (c->have_rsa3072)
-      hipLaunchKernelGGL((k_rsa_modexp<MONT_L3072, MONT_TPI_BIG>), qg8, dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
+    if (mg.m3072)
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L3072, MONT_TPI_BIG>), dim3(mg.m3072), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
                          cnt_p + 2, start + 2, c->kt, c->r3072.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr);
-    if (c->have_rsa4096)
-      hipLaunchKernelGGL((k_rsa_modexp<MONT_L4096, MONT_TPI_BIG>), qg8, dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list4096.as<uint32_t>(),
+    if (mg.m4096)
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L4096, MONT_TPI_BIG>), dim3(mg.m4096), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list4096.as<uint32_t>(),
                          cnt_p + 3, start + 3, c->kt, c->r4096.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr);
   };
   static const bool turnstile_off = getenv("BFTKV_NO_TURNSTILE") != nullptr;      // (read once: this is every big call's path)
-  const bool big = staged_cap ? (ev_input != nullptr && ss_len / 320 >= TURNSTILE_MIN_PACKETS) : total >= TURNSTILE_MIN_PACKETS;
-  if (big && !turnstile_off) {
+  // a launch that fills the machine takes its turn behind the modexp of whichever context went last
+  auto at_turnstile = [&](const std::function<void()>& launch, bool stamp) -> hipError_t {
     Turnstile& g = g_turnstile[(unsigned)c->device & 15u];
     std::lock_guard<std::mutex> tl(g.mu);
-    if (g.last && g.owner != c) HIPCHK(c, hipStreamWaitEvent(s, g.last, 0));
-    HIPCHK(c, rec(9, s));
-    launch_modexp(start0);
-    if (!c->ev_turn) HIPCHK(c, hipEventCreateWithFlags(&c->ev_turn, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_turn, s));
+    hipError_t e = hipSuccess;
+    if (g.last && g.owner != c && (e = hipStreamWaitEvent(s, g.last, 0)) != hipSuccess) return e;
+    if (stamp && (e = rec(9, s)) != hipSuccess) return e;
+    launch();
+    if (!c->ev_turn && (e = hipEventCreateWithFlags(&c->ev_turn, hipEventDisableTiming)) != hipSuccess) return e;
+    if ((e = hipEventRecord(c->ev_turn, s)) != hipSuccess) return e;
     g.last = c->ev_turn; g.owner = c;
+    return hipSuccess;
+  };
+  // by the report: the pass over the values too long for the 29-bit form waits for the plan's word, behind the wait below
+  ModexpGrids mg1 = mg_total;
+  if (by_report) mg1.wide = 0;
+  if (big && !turnstile_off) {
+    HIPCHK(c, at_turnstile([&] { launch_modexp(start0, mg1); }, true));
   } else {
     HIPCHK(c, rec(9, s));
-    if (total) launch_modexp(start0);
+    if (total) launch_modexp(start0, mg1);
   }
   HIPCHK(c, rec(2, s));
   if (upload_tbs) {
     int hrc = (*upload_tbs)(sh);
     if (hrc) return hrc;
     if (!mid_prelaunched)
-      hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + 63) / 64), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
+      hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + MID_BLOCK - 1) / MID_BLOCK), dim3(MID_BLOCK), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
     if ((hrc = hash_stream_work())) return hrc;
   }
-  HIPCHK(c, join(s, 6));
+  if (!by_report) HIPCHK(c, join(s, 6));
   // digests of the hashes other than SHA-256: on the MAIN stream, after the modexp.  Normally there are none and the kernel
   // exits on a device-side flag; at its 203 VGPRs it cannot co-schedule beside k_rsa_modexp, and on the hash stream it sat
   // there until the modexp drained (1.7 ms per step in the trace) holding back the join.
@@ -813,35 +856,91 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   bool other_hashes = true;
   if (total && !d_mid_in && plan_q && big && c->h_mail) {
     const auto t_spin = std::chrono::steady_clock::now();
+    // by the report: also for the four list lengths, which the plan's LAST block sends -- under the same deadline.  What that
+    // costs: the flags word leaves with the plan's first block, the lengths with its last, so the calling thread spins for the
+    // plan's own duration more than it did, and beside a neighbour's modexp, where the plan is starved for block slots, usually
+    // to the deadline (cfg 2, three in flight: 0.57 ms per call, the lengths in time in 5 calls of 28; docs/history.md
+    // 2026-10-21).  Nothing tells the host sooner that the plan is complete: the lengths are that signal.  The hash stream's
+    // work needs the flags word alone and is enqueued the moment it is read.
+    bool hashed = false;
     for (uint32_t it = 0;; ++it) {
-      const uint32_t v = __atomic_load_n(&c->h_mail[3], __ATOMIC_ACQUIRE);
-      if (v) { other_hashes = (v & 1u) != 0; break; }
+      const uint32_t v = __atomic_load_n(&c->h_mail[plan_report::MAIL_PLAN_FLAGS], __ATOMIC_ACQUIRE);
+      if (v) {
+        other_hashes = (v & plan_report::FLAG_OTHER_HASH) != 0;
+        rin.flags_word = v;
+        if (!by_report) break;
+        if (!hashed) {
+          dec = plan_report::decide(rin, geo);      // (for the midstates of the other hashes: the flags are all they depend on)
+          int hrc = hash_stream_work(); if (hrc) return hrc;
+          hashed = true;
+        }
+        bool all = true;
+        for (int k = 0; k < plan_report::N_LISTS; ++k) {
+          rin.len_word[k] = __atomic_load_n(&c->h_mail[plan_report::MAIL_LEN0 + k], __ATOMIC_ACQUIRE);
+          all = all && rin.len_word[k] != 0;
+        }
+        if (all) break;
+      }
       // (the parse and the plan of a big batch take milliseconds themselves: ~0.1 ns per packet each, more beside a neighbour's modexp)
       if ((it & 255u) == 255u && std::chrono::steady_clock::now() - t_spin > std::chrono::microseconds(300) + std::chrono::nanoseconds((uint64_t)total / 2)) break;
       __builtin_ia32_pause();
     }
+    if (by_report && !hashed) { int hrc = hash_stream_work(); if (hrc) return hrc; }      // (no flags word: `dec` still says "launch them")
+  }
+  rin.dsa_inv_batched = inv_batch_min != 0xFFFFFFFFu; rin.dsa_inv_single = inv_batch_min != 0u;
+  if (report_path) {
+    dec = plan_report::decide(rin, geo);
+    plan_report::flatten(dec, rin, c->last_plan_report);
+    c->have_plan_report = true;
+  }
+  if (by_report) {
+    // The pass over the long values waited for the flags word.  With the bit read, it fills the machine as any modexp does and
+    // takes a turn at the turnstile of its own: this call's compare and phase 2 then stand behind the neighbour's modexp that
+    // went in between, and the call publishes a new turn.  With no flags word at the deadline the grid is the one it always was,
+    // normally empty, and goes straight behind this call's modexp on the stream WITHOUT a turn: the parent had it inside the
+    // main modexp's turn, so here a neighbour admitted after that turn may run beside it.  (Either way it lies behind event 2:
+    // bftkv_gpu_last_timing's modexp figure does not include it.)
+    const ModexpGrids mgw{0u, dec.p1.wide, 0u, 0u};
+    if (mgw.wide) {
+      if (!turnstile_off && dec.flags_used) HIPCHK(c, at_turnstile([&] { launch_modexp(start0, mgw); }, false));
+      else launch_modexp(start0, mgw);
+    }
+    HIPCHK(c, join(s, 6));
   }
   if (total && !d_mid_in && other_hashes)
     hipLaunchKernelGGL(k_digest_other, dim3(std::min<uint32_t>((total + 255) / 256, DIGEST_OTHER_MAX_BLOCKS)), dim3(256), 0, s,
                        d_tbs, d_tbs_off, d_ss, c->mid.as<uint32_t>(), c->mid64.as<uint64_t>(), n_items, c->recs.as<SigRec>(), total,
                        c->digests.as<uint32_t>(), c->pk_count.as<uint32_t>() + 4, txt, n_recs_dev);
-  const dim3 cg(((uint64_t)total * CMP_LANES + 255) / 256);
-  auto launch_compare = [&](const uint32_t* start) {
-    hipLaunchKernelGGL(k_rsa_compare, cg, dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                       cnt_p, start, c->kt, c->r.as<uint32_t>(), c->digests.as<uint32_t>());
-    if (c->have_rsa3072)
-      hipLaunchKernelGGL(k_rsa_compare, cg, dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
+  // grids of a phase: over `total` as ever (blocks beyond the device-side count exit at once), or -- the resident big call --
+  // over what the plan reported
+  const uint32_t cg = (uint32_t)(((uint64_t)total * CMP_LANES + 255) / 256);
+  plan_report::PhaseGrids pg_total;
+  pg_total.compare[plan_report::L_RSA2048] = cg;
+  pg_total.compare[plan_report::L_RSA3072] = c->have_rsa3072 ? cg : 0u;
+  pg_total.compare[plan_report::L_RSA4096] = c->have_rsa4096 ? cg : 0u;
+  pg_total.dsa_mul = (total + 63) / 64; pg_total.dsa_split = c->have_dsa3072 && c->have_dsa2048 ? (total + 255) / 256 : 0u;
+  pg_total.dsa_modexp4 = c->have_dsa2048 ? (total + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK : 0u;
+  pg_total.dsa_modexp8 = c->have_dsa3072 ? (total + RSA_BLOCK / MONT_TPI_BIG - 1) / (RSA_BLOCK / MONT_TPI_BIG) : 0u;
+  const plan_report::PhaseGrids& pg1 = report_path ? dec.p1 : pg_total;
+  const plan_report::PhaseGrids& pg2 = report_path ? dec.p2 : pg_total;
+  auto launch_compare = [&](const uint32_t* start, const plan_report::PhaseGrids& pg) {
+    if (pg.compare[plan_report::L_RSA2048])
+      hipLaunchKernelGGL(k_rsa_compare, dim3(pg.compare[plan_report::L_RSA2048]), dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->digests.as<uint32_t>());
+    if (pg.compare[plan_report::L_RSA3072])
+      hipLaunchKernelGGL(k_rsa_compare, dim3(pg.compare[plan_report::L_RSA3072]), dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
                          cnt_p + 2, start + 2, c->kt, c->r3072.as<uint32_t>(), c->digests.as<uint32_t>());
-    if (c->have_rsa4096)
-      hipLaunchKernelGGL(k_rsa_compare, cg, dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list4096.as<uint32_t>(),
+    if (pg.compare[plan_report::L_RSA4096])
+      hipLaunchKernelGGL(k_rsa_compare, dim3(pg.compare[plan_report::L_RSA4096]), dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list4096.as<uint32_t>(),
                          cnt_p + 3, start + 3, c->kt, c->r4096.as<uint32_t>(), c->digests.as<uint32_t>());
   };
   // DSA signatures (if any): u1 depends on the digest, so the table multiplications run after the join; the
-  // inverses were started on their own stream right after the parse.  Grids cover every signature and exit on
-  // the device-side count, so no host read-back sits between the kernels.
-  auto launch_dsa = [&](const uint32_t* start) {
-    hipLaunchKernelGGL(k_dsa_mul, dim3((total + 63) / 64), dim3(64), 0, s, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(),
-                       cnt_p, start, c->kt, c->digests.as<uint32_t>(), c->dsa_u.as<uint32_t>());
+  // inverses were started on their own stream right after the parse.  Grids cover every signature that can be in the list and
+  // exit on the device-side count, so no host read-back sits between the kernels.
+  auto launch_dsa = [&](const uint32_t* start, const plan_report::PhaseGrids& pg) {
+    if (pg.dsa_mul)
+      hipLaunchKernelGGL(k_dsa_mul, dim3(pg.dsa_mul), dim3(64), 0, s, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->digests.as<uint32_t>(), c->dsa_u.as<uint32_t>());
     // (the LDS-DMA form of this kernel measured the same and spilled: removed in round 5, profiles/r04_cfg3_ab_dsa_dma*.json)
     // a key table with DSA keys of both size classes: the list's positions sorted by class first (phase 1: counters [20], [21];
     // phase 2: [22], [23]), each instantiation over its own compact list; one class only: that instantiation over the list itself
@@ -849,22 +948,23 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     if (c->have_dsa3072 && c->have_dsa2048) {
       uint32_t* cc = cnt_p + (start == start0 ? 20 : 22);
       uint32_t* is = c->dsa_idx.as<uint32_t>() + (start == start0 ? 0 : 2 * (size_t)total);
-      hipLaunchKernelGGL(k_dsa_split, dim3((total + 255) / 256), dim3(256), 0, s, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(), cnt_p, start, c->kt,
-                         is, is + total, cc);
+      if (pg.dsa_split)
+        hipLaunchKernelGGL(k_dsa_split, dim3(pg.dsa_split), dim3(256), 0, s, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(), cnt_p, start, c->kt,
+                           is, is + total, cc);
       idx_s = is; idx_b = is + total; cnt_cls = cc;
     }
-    if (c->have_dsa2048)
-      hipLaunchKernelGGL((k_dsa_modexp<MONT_L, MONT_TPI>), dim3((total + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK), dim3(RSA_BLOCK), 0, s,
+    if (pg.dsa_modexp4)
+      hipLaunchKernelGGL((k_dsa_modexp<MONT_L, MONT_TPI>), dim3(pg.dsa_modexp4), dim3(RSA_BLOCK), 0, s,
                          c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(), cnt_p, start, c->kt, c->dsa_u.as<uint32_t>(), idx_s, cnt_cls);
-    if (c->have_dsa3072)      // keys with p beyond 2048 bits: the 8-lane form
-      hipLaunchKernelGGL((k_dsa_modexp<MONT_L3072, MONT_TPI_BIG>), dim3((total + RSA_BLOCK / MONT_TPI_BIG - 1) / (RSA_BLOCK / MONT_TPI_BIG)), dim3(RSA_BLOCK), 0, s,
+    if (pg.dsa_modexp8)      // keys with p beyond 2048 bits: the 8-lane form
+      hipLaunchKernelGGL((k_dsa_modexp<MONT_L3072, MONT_TPI_BIG>), dim3(pg.dsa_modexp8), dim3(RSA_BLOCK), 0, s,
                          c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(), cnt_p, start, c->kt, c->dsa_u.as<uint32_t>(), idx_b, cnt_cls ? cnt_cls + 1 : nullptr);
   };
-  if (total) launch_compare(start0);
+  if (total) launch_compare(start0, pg1);
   HIPCHK(c, rec(8, s));
   if (total && c->have_dsa_keys) {
     HIPCHK(c, hipStreamWaitEvent(s, c->ev[7], 0));
-    launch_dsa(start0);
+    launch_dsa(start0, pg1);
   }
   if (total && plan_q) {
     // phase 2: tally what phase 1 verified; whatever an item still lacks comes from its remaining packets
@@ -876,10 +976,22 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     pl.verdict = c->o_verdict.as<uint8_t>();
     hipLaunchKernelGGL(k_plan<2>, dim3((n_items + PLAN_ITEMS - 1) / PLAN_ITEMS), dim3(PLAN_BLOCK), 0, s, pl, c->kt, *plan_q);
     const uint32_t* const start1 = cnt_p + 8;
-    if (c->have_dsa_keys) launch_dsa_inv(s, start1);
-    launch_modexp(start1);
-    launch_compare(start1);
-    if (c->have_dsa_keys) launch_dsa(start1);
+    if (!by_report) {
+      if (c->have_dsa_keys) launch_dsa_inv(s, start1, total);
+      launch_modexp(start1, mg_total);
+    } else {
+      // no list can grow by more than the packets phase 1 left unqueued (dec.phase2_bound; `total` without the plan's words)
+      if (c->have_dsa_keys && dec.phase2_bound) launch_dsa_inv(s, start1, dec.phase2_bound);
+      launch_modexp(start1, ModexpGrids{dec.modexp2, 0u, dec.modexp2_3072, dec.modexp2_4096});
+      // (the long values: behind a turn at the turnstile when this call sizes by the report, as in phase 1)
+      const ModexpGrids mgw{0u, dec.p2.wide, 0u, 0u};
+      if (mgw.wide) {
+        if (!turnstile_off && dec.flags_used) HIPCHK(c, at_turnstile([&] { launch_modexp(start1, mgw); }, false));
+        else launch_modexp(start1, mgw);
+      }
+    }
+    launch_compare(start1, pg2);
+    if (c->have_dsa_keys) launch_dsa(start1, pg2);
   }
   // several keys under one key id: what the candidates behind the first do to the status of a record it did not verify
   // (never to a verdict: see the kernel)
@@ -1966,7 +2078,7 @@ static int collective_verify_pipelined(bftkv_gpu_ctx* c, int quorum, uint32_t n_
       bftkv_gpu_ctx* w = c->hb_workers[next_mid];
       const uint32_t n = pc[next_mid].i1 - pc[next_mid].i0;
       if (w->mid.ensure(sizeof(uint32_t) * 8 * N_MID32 * (size_t)n + 16) != hipSuccess) return -1;
-      hipLaunchKernelGGL(k_sha256_mid, dim3((n + 63) / 64), dim3(64), 0, w->stream_h, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>() + pc[next_mid].i0, n,
+      hipLaunchKernelGGL(k_sha256_mid, dim3((n + MID_BLOCK - 1) / MID_BLOCK), dim3(MID_BLOCK), 0, w->stream_h, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>() + pc[next_mid].i0, n,
                          w->mid.as<uint32_t>());
       tr[8 + HB_TR * next_mid + 3] = us_now();
       ++next_mid;
@@ -2352,6 +2464,15 @@ int bftkv_gpu_last_sclk_mhz(bftkv_gpu_ctx* c, float* mhz) {
   uint64_t v[2] = {0, 0};
   if (c->pk_count.p) HIPCHK(c, hipMemcpy(v, (const char*)c->pk_count.p + 64, 16, hipMemcpyDeviceToHost));
   *mhz = v[1] ? (float)((double)v[0] / (double)v[1] * 100.0) : 0.0f;
+  return 0;
+}
+
+int bftkv_gpu_last_plan_report(bftkv_gpu_ctx* c, uint32_t* out, uint32_t cap, uint32_t* n_out) {
+  if (!c || !n_out || (cap && !out)) return BFTKV_E_INVALID;
+  ctx_lock lk(c->mu);
+  if (!c->have_plan_report) return fail(c, BFTKV_E_STATE, "the last call was not sized by a plan report");
+  *n_out = plan_report::N_SLOTS;
+  for (uint32_t k = 0; k < cap && k < (uint32_t)plan_report::N_SLOTS; ++k) out[k] = c->last_plan_report[k];
   return 0;
 }
 

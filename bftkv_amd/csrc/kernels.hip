@@ -28,6 +28,7 @@
 #include "value_load.h"
 #include "u256.h"
 #include "hashes.h"
+#include "plan_report.h"
 
 namespace bftkv {
 
@@ -912,27 +913,39 @@ __global__ void __launch_bounds__(64) k_signers(const uint8_t* __restrict__ sig_
 // single-block exclusive scan (n up to a few million): each thread scans a contiguous chunk
 // `host_total` (optional) is a mapped, pinned host word: the host spins on it instead of paying an interrupt-driven
 // stream synchronisation for the one number it needs (arena and grid sizes) in the middle of the pipeline.
-// The kernel also clears what the parse accumulates into (the 24 work-list words, the per-item hash masks): two memset
+// The kernel also clears what the parse accumulates into (the work-list words, the per-item hash masks): two memset
 // launches fewer per call.
+// With `item_flags`, the mailbox also receives how many items overflowed their walk scratch row (walk_cap): none, and the
+// host does not launch the fill pass k_walk<true>.
+constexpr uint32_t PK_COUNT_WORDS = 32;      // the per-call counters behind pk_count (run_pipeline lists them)
+constexpr uint32_t PK_PLAN_TICKET = 24;      // ... of which: blocks of k_plan<1> that have queued their share
 // `cap` (staged small calls, which size their arena from the stream length instead of asking the host in mid-pipeline): a
 // call with more packet events than that becomes an EMPTY call -- every count zero, total[1] = the real total -- and the
 // caller runs it again through the ordinary entry point.
 __global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ counts, uint32_t n,
                                                       uint32_t* __restrict__ base, uint32_t* __restrict__ total,
-                                                      uint32_t* __restrict__ host_total, uint32_t* __restrict__ pk_count /*[24] or null*/,
+                                                      uint32_t* __restrict__ host_total, uint32_t* __restrict__ pk_count /*[PK_COUNT_WORDS] or null*/,
                                                       uint32_t* __restrict__ item_hash_mask /*[n] or null*/, uint32_t cap,
                                                       uint32_t* __restrict__ chunk_ctr /*[4] or null: [0] arena units the walk asked
-                                                        for (zeroed here for the next call), [1] the parse's bump, [2] copy of [0]*/) {
+                                                        for (zeroed here for the next call), [1] the parse's bump, [2] copy of [0]*/,
+                                                      const uint8_t* __restrict__ item_flags = nullptr /*[n] or null*/, uint32_t walk_cap = 0) {
   __shared__ uint32_t part[1024];
+  __shared__ uint32_t n_over;      // items whose event list the fill pass of the walk has to write (host mailbox only)
   uint32_t t = threadIdx.x;
   uint32_t chunk = (n + 1023) / 1024;
   uint32_t lo = t * chunk, hi = min(n, lo + chunk);
   uint32_t s = 0;
+  if (t == 0) n_over = 0;
   for (uint32_t i = lo; i < hi; ++i) s += counts[i];
   part[t] = s;
-  if (pk_count && t < 24) pk_count[t] = 0;
+  if (pk_count && t < PK_COUNT_WORDS) pk_count[t] = 0;
   if (item_hash_mask) for (uint32_t i = lo; i < hi; ++i) item_hash_mask[i] = 0;
   __syncthreads();
+  if (host_total && item_flags) {      // the condition under which k_walk<true> does not return at once
+    uint32_t over = 0;
+    for (uint32_t i = lo; i < hi; ++i) over += (counts[i] > walk_cap || (item_flags[i] & 2)) ? 1u : 0u;
+    if (over) atomicAdd(&n_over, over);
+  }
   for (uint32_t off = 1; off < 1024; off <<= 1) {
     uint32_t v = (t >= off) ? part[t - off] : 0;
     __syncthreads();
@@ -953,6 +966,7 @@ __global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ cou
     if (chunk_ctr) { units = chunk_ctr[0]; chunk_ctr[0] = 0; chunk_ctr[1] = 0; chunk_ctr[2] = units; }
     if (host_total) {
       host_total[2] = units;      // (ahead of the release below: the host reads it after the packet count)
+      host_total[plan_report::MAIL_OVERFLOW] = item_flags ? n_over : 0xFFFFFFFFu;      // (the scan loop's barriers lie behind the adds)
       __hip_atomic_store(host_total, all, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
@@ -985,7 +999,16 @@ __device__ __forceinline__ void load_block_be(const uint8_t* p, uint32_t (&w)[16
 // Thread per item, one compression after the other: the loop is a chain of (uncoalesced) block loads and 64 rounds.
 // The next block's 17 dwords are requested before the current block is compressed, so the load latency hides behind
 // the rounds (two blocks per trip, no register shuffling).
-__global__ void __launch_bounds__(64) k_sha256_mid(const uint8_t* __restrict__ tbs_blob, const uint64_t* __restrict__ tbs_off,
+// Block size: one thread per item either way.  At 64 the 157 one-wave blocks of a 10,000-item batch each hold one SIMD's registers
+// for the length of the chain (0.4 ms), and while they do the three other SIMDs of those CUs cannot take a four-wave modexp block of
+// a neighbouring batch; at 256 forty four-wave blocks hold forty block slots.  Measured with three batches in flight: 2.50 against
+// 2.57 ms per cfg-2 step (-DBFTKV_MID_BLOCK=64|256, docs/history.md 2026-10-21).
+#ifndef BFTKV_MID_BLOCK
+#define BFTKV_MID_BLOCK 256
+#endif
+constexpr int MID_BLOCK = BFTKV_MID_BLOCK;
+static_assert(MID_BLOCK == 64 || MID_BLOCK == 256, "k_sha256_mid: one wave or four per block");
+__global__ void __launch_bounds__(MID_BLOCK) k_sha256_mid(const uint8_t* __restrict__ tbs_blob, const uint64_t* __restrict__ tbs_off,
                                                    uint32_t n_items, uint32_t* __restrict__ mid /*[n][8]*/) {
   uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= n_items) return;
@@ -2321,7 +2344,8 @@ struct PlanArgs {
   uint32_t* plan_cut;          // [n_items] records covered so far
   const uint8_t* verdict;      // phase 2: verdict bits of the phase-1 tally
   uint32_t margin;
-  uint32_t* mail;              // phase 1: mapped host word that receives 0x80000000 | (some signature uses a hash other than SHA-256)
+  uint32_t* mail;              // phase 1: mapped host words (plan_report.h, from MAIL_PLAN_FLAGS on): the flags word from the first block,
+                               // the four list lengths from the block that finishes last
 };
 
 // One wave per item, 16 items per block.  Work-list slots come from ONE atomic per block and list: every wave first counts
@@ -2335,8 +2359,10 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanArgs a, KeyTableDev kt,
   const uint32_t wib = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t item = blockIdx.x * PLAN_ITEMS + wib;
   // the parse is complete: tell the host whether k_digest_other has anything to do, so that it need not launch it
+  // ... and whether the 19 x 4 pass over values too long for the 29-bit form has
   if (PHASE == 1 && a.mail && blockIdx.x == 0 && threadIdx.x == 0)
-    __hip_atomic_store(a.mail, 0x80000000u | (a.pk_count[4] ? 1u : 0u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(a.mail, plan_report::ARRIVED | (a.pk_count[4] ? plan_report::FLAG_OTHER_HASH : 0u) |
+                               (a.pk_count[5] ? plan_report::FLAG_WIDE_VALUE : 0u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   const bool have = item < a.n_items;
   const uint32_t base = have ? a.rec_base[item] : 0, cnt = have ? a.counts[item] : 0;
   uint32_t* const lists[4] = {a.pk_list, a.dsa_list, a.pk_list3072, a.pk_list4096};
@@ -2421,6 +2447,19 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanArgs a, KeyTableDev kt,
     }
   }
   if (have && lane == 0) a.plan_cut[item] = (PHASE == 1) ? covered : cnt;
+  // The block that finishes last tells the host how long the four work lists are after phase 1: the host sizes what it
+  // enqueues behind the modexp by them (plan_report.h).  Every block's additions to the list lengths lie before the barrier
+  // above, its ticket behind it; the lengths are read where the additions were made.
+  if (PHASE == 1 && a.mail && threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(a.pk_count + PK_PLAN_TICKET, 1u) == gridDim.x - 1) {
+      __threadfence();
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        __hip_atomic_store(a.mail + (plan_report::MAIL_LEN0 - plan_report::MAIL_PLAN_FLAGS) + k,
+                           plan_report::ARRIVED | atomicAdd(a.pk_count + k, 0u), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
 }
 
 // the work-list lengths at the end of phase 1 become phase 2's start offsets

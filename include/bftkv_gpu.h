@@ -957,6 +957,16 @@ int bftkv_gpu_last_timing(bftkv_gpu_ctx* ctx, float ms[8]);
  * of its first wave; 0 when the call queued no RSA work.  The part clocks down under an all-MAC load, and the integer roof
  * of the path moves with it. */
 int bftkv_gpu_last_sclk_mhz(bftkv_gpu_ctx* ctx, float* mhz);
+/* What the last bftkv_gpu_collective_verify_dev call launched behind its modexp, when it was a resident big call under the
+ * early exit (98,304 packets or more): such a call sizes those launches by what the device reported about the batch
+ * (csrc/plan_report.h; BFTKV_PLAN_REPORT=0 in the environment: by the packet count, as every other call does).
+ * out[k] = blocks of launch k, 0 = not launched, in the order of plan_report.h's `Slot`: [0] bit 0 the plan's flags word was
+ * used, bit 1 its list lengths, bit 2 the scan's overflow count, bit 3 the report is enabled; [1] the packets phase 2 could
+ * still queue; [2] the walk's fill pass; [3], [4] midstates of the other hashes (payload, text); [5..12] phase 1: wide-value
+ * modexp, compare (<= 2048, 3072, 4096), DSA mul, split, modexp (4, 8 lanes); [13..25] phase 2: modexp, wide-value modexp,
+ * modexp 3072, 4096, compare x 3, DSA inverse (batched, single), mul, split, modexp (4, 8 lanes); [26] packets of the call.
+ * *n_out = the number of slots (27); at most `cap` are written.  BFTKV_E_STATE when the last call was of another kind. */
+int bftkv_gpu_last_plan_report(bftkv_gpu_ctx* ctx, uint32_t* out, uint32_t cap, uint32_t* n_out);
 void* bftkv_gpu_stream(bftkv_gpu_ctx* ctx);   /* hipStream_t of the context */
 
 #ifdef __cplusplus

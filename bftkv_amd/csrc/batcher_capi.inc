@@ -108,10 +108,13 @@ int staged_verify(bftkv_gpu_ctx* c, const StagedCall& L, uint8_t* pin, const uin
   int rc;
   const uint8_t* res;
   uint32_t from_verdict;
+  PipelineCall call;      // tails and midstates instead of payloads, sized up front
+  call.n_items = n; call.d_tbs = d_tails; call.d_tbs_off = d_toff; call.d_ss = d_ss; call.d_ss_off = d_soff; call.ss_len = L.ss_len;
+  call.d_mid_in = d_mid; call.d_tbs_prefix = d_prefix;
   // Arena and grids for `cap` packet events, no host round trip in mid-pipeline (run_pipeline, staged_cap).  A signature
   // packet of the path's writers is 100 (DSA) to 540 (RSA-4096) bytes; one event per 16 stream bytes leaves room for streams
   // of junk packets, and a call beyond it comes back marked for the ordinary path.
-  const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, L.ss_len / 16 + 64 * (uint64_t)n), 1u << 26);
+  call.staged_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096, L.ss_len / 16 + 64 * (uint64_t)n), 1u << 26);
   // Every packet of every item is verified (no two-phase planning): err and n_verified are the reference's either way, a
   // small call is bound by its chain of launches, not by the 20 % of modexps the planning saves, and it is seven launches
   // shorter.
@@ -120,8 +123,7 @@ int staged_verify(bftkv_gpu_ctx* c, const StagedCall& L, uint8_t* pin, const uin
     QuorumHost& q = c->quorums[L.quorum];
     if ((rc = build_member(c, q))) return rc;
     const QuorumDev qd = quorum_dev(c, q);
-    if ((rc = run_pipeline(c, n, d_tails, d_toff, d_ss, d_soff, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, L.ss_len, d_mid, d_prefix, cap)))
-      return rc;
+    if ((rc = run_pipeline(c, call))) return rc;
     HIPCHK(c, c->o_nver.ensure(sizeof(uint32_t) * n));
     HIPCHK(c, c->o_verdict.ensure(n));
     hipLaunchKernelGGL(k_tally, dim3((n + 3) / 4), dim3(256), 0, c->stream, c->recs.as<SigRec>(), c->base.as<uint32_t>(), c->counts.as<uint32_t>(), n,
@@ -129,8 +131,8 @@ int staged_verify(bftkv_gpu_ctx* c, const StagedCall& L, uint8_t* pin, const uin
     res = c->o_verdict.as<uint8_t>();
     from_verdict = 1;
   } else {
-    if ((rc = run_pipeline(c, n, d_tails, d_toff, d_ss, d_soff, d_cert, nullptr, nullptr, nullptr, nullptr, nullptr, L.ss_len, d_mid, d_prefix, cap)))
-      return rc;
+    call.d_cert_ent = d_cert;
+    if ((rc = run_pipeline(c, call))) return rc;
     HIPCHK(c, c->o_err.ensure(n));
     hipLaunchKernelGGL(k_sigverify_fold, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->recs.as<SigRec>(), c->base.as<uint32_t>(),
                        c->counts.as<uint32_t>(), c->item_flags.as<uint8_t>(), n, c->o_err.as<uint8_t>());

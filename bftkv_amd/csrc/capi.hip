@@ -559,114 +559,81 @@ __global__ void __launch_bounds__(256) k_tally_ids(const uint64_t* __restrict__ 
   }
 }
 
-// Shared pipeline.  Main stream: walk -> parse -> RSA modexp -> compare.  Hash stream (forked after
-// the parse): SHA-256 midstates -> per-signature digests; joined before the compare.  Leaves SigRec
-// statuses final.
-int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const uint64_t* d_tbs_off,
-                 const uint8_t* d_ss, const uint64_t* d_ss_off, const uint32_t* d_cert_ent, const uint8_t* d_sig_class = nullptr,
-                 const uint32_t* d_msg_slot = nullptr, const uint8_t* d_msg_hash = nullptr,
-                 const std::function<int(hipStream_t)>* upload_tbs = nullptr, const QuorumDev* plan_q = nullptr, uint64_t ss_len = 0,
-                 const uint32_t* d_mid_in = nullptr, const uint64_t* d_tbs_prefix = nullptr, uint32_t staged_cap = 0,
-                 hipEvent_t ev_input = nullptr, bool mid_prelaunched = false, const uint64_t* d_forced_issuer = nullptr) {
+// What a caller asks of run_pipeline, by name.  A call is a combination of these, not one of N kinds; fields left alone: a
+// resident call that verifies every packet of every item against the node keyring.
+struct PipelineCall {
+  uint32_t n_items = 0;
+  const uint8_t* d_tbs = nullptr; const uint64_t* d_tbs_off = nullptr;      // the signed payloads and their [n_items + 1] offsets
+  const uint8_t* d_ss = nullptr; const uint64_t* d_ss_off = nullptr;        // the signature streams, likewise
+  uint64_t ss_len = 0;                        // bytes of d_ss (0: not known): sizes the walk's scratch row and a staged call's arena
+  const uint32_t* d_cert_ent = nullptr;       // per item or null: the one entity whose keys may verify it (ParseArgs::cert_ent)
+  const uint8_t* d_sig_class = nullptr;       // per item or null: the certificate check the item is (ParseArgs::sig_class)
+  const uint64_t* d_forced_issuer = nullptr;  // per item or null, with d_sig_class: the key the caller holds (ParseArgs::forced_issuer)
+  const uint32_t* d_msg_slot = nullptr;       // transport messages: per item the sender's slot and the hash its signature names
+  const uint8_t* d_msg_hash = nullptr;        // (ParseArgs::msg_slot, msg_hash)
+  // upload_tbs (host-buffer entry point): the signed payloads are still in host memory.  Only the hash stream reads them,
+  // so their copy is issued on that stream AFTER the modexp has been launched and runs beside it; the signature stream
+  // (which the walk, the parse and the modexp need) was copied before the call.
+  const std::function<int(hipStream_t)>* upload_tbs = nullptr;
   // mid_prelaunched (pieces of a pipelined host-buffer call): the caller has already put k_sha256_mid for these items on the
   // hash stream -- when the payloads arrived, ahead of the signature streams -- so the chain of 134 dependent compressions per
   // payload is under way before the piece is picked up.
+  bool mid_prelaunched = false;
   // ev_input (pipelined host-buffer calls): the signature streams and offsets of this call are still being copied by another
   // stream; the main stream waits for that event first (the hash stream joins the main stream's start, so it waits too).
-  // staged_cap (staged small calls): the arena and the grids are sized for that many packet events up front and the
-  // kernels read the real count from the device -- no host round trip in mid-pipeline; a call with more events turns
-  // itself into an empty one (k_scan_counts) and is run again through the ordinary path by its caller.
+  hipEvent_t ev_input = nullptr;
+  // plan_q (CollectiveSignature.Verify with the early exit enabled): public-key work is queued in two phases by k_plan
+  // instead of by the parse -- see kernels.hip "two-phase planning".
+  const QuorumDev* plan_q = nullptr;
   // d_mid_in / d_tbs_prefix (the micro-batcher, whose callers absorb the whole blocks of their payload on their own threads):
   // SHA-256 midstates [n_items][8] and the byte counts behind them; d_tbs then holds only the < 64 bytes after each.  No
   // payload hashing on the device; a signature that asks for another hash stays ST_PENDING_HASH (the caller re-submits
   // such an item with its payload: k_fenced_out's rehash bit).
-  // plan_q (CollectiveSignature.Verify with the early exit enabled): public-key work is queued in two phases by k_plan
-  // instead of by the parse -- see kernels.hip "two-phase planning".
-  // upload_tbs (host-buffer entry point): the signed payloads are still in host memory.  Only the hash stream reads them,
-  // so their copy is issued on that stream AFTER the modexp has been launched and runs beside it; the signature stream
-  // (which the walk, the parse and the modexp need) was copied before the call.
-  // A staged small call keeps its hashing on the main stream: its digest kernel is a few microseconds, two cross-stream joins
-  // cost more than that, and a lane that occupies ONE hardware queue leaves the others to the other lanes (the runtime maps
-  // streams onto 4 queues by default: three streams per lane made four lanes run one after the other).
-  // (a capped call that waits for its input on an event is a PIECE of a pipelined host-buffer call: big, so it keeps the side
-  // streams and the turnstile of a resident batch, and like a staged call it never asks the host for its packet count)
-  const bool one_stream = staged_cap != 0 && !ev_input;
-  hipStream_t s = c->stream, sh = one_stream ? c->stream : c->stream_h;
-  auto rec = [&](int k, hipStream_t st) -> hipError_t { return one_stream ? hipSuccess : hipEventRecord(c->ev[k], st); };
-  auto join = [&](hipStream_t st, int k) -> hipError_t { return one_stream ? hipSuccess : hipStreamWaitEvent(st, c->ev[k], 0); };
-  if (!c->ev[0]) for (auto& e : c->ev) HIPCHK(c, hipEventCreate(&e));
+  const uint32_t* d_mid_in = nullptr; const uint64_t* d_tbs_prefix = nullptr;
+  // staged_cap (staged small calls): the arena and the grids are sized for that many packet events up front and the
+  // kernels read the real count from the device -- no host round trip in mid-pipeline; a call with more events turns
+  // itself into an empty one (k_scan_counts) and is run again through the ordinary path by its caller.
+  uint32_t staged_cap = 0;
+};
+
+constexpr uint32_t MAIL_EMPTY = 0xFFFFFFFFu;      // mailbox word 0 until the scan has written the packet count
+
+// the buffers sized by the item count (before the packet count is known)
+static int ensure_for_items(bftkv_gpu_ctx* c, const PipelineCall& call, uint32_t walk_cap, TextDev* txt) {
+  const size_t n_items = call.n_items;
   HIPCHK(c, c->counts.ensure(sizeof(uint32_t) * (n_items + 1)));
   HIPCHK(c, c->base.ensure(sizeof(uint32_t) * (n_items + 1)));
   HIPCHK(c, c->total.ensure(16));
   HIPCHK(c, c->item_flags.ensure(n_items + 16));
-  // walk scratch row: sized from the average stream length (a packet event needs >= 2 stream bytes, a signature ~100..300);
-  // items with more events than the row holds take the sequential fill pass
-  const uint32_t walk_cap = ss_len ? (uint32_t)std::min<uint64_t>(WALK_CAP_MAX, std::max<uint64_t>(WALK_CAP_MIN, ss_len / n_items / 48)) : 96u;
-  HIPCHK(c, c->walk_scratch.ensure(sizeof(WalkEnt) * walk_cap * (size_t)n_items + 16));
-  HIPCHK(c, c->mid.ensure(sizeof(uint32_t) * 8 * N_MID32 * (size_t)n_items + 16));      // SHA-256 | SHA-224 | SHA-1 | MD5 | RIPEMD-160 midstates
-  HIPCHK(c, c->mid64.ensure(sizeof(uint64_t) * 8 * 2 * (size_t)n_items + 16));   // SHA-512 | SHA-384
-  HIPCHK(c, c->hash_mask.ensure(sizeof(uint32_t) * (size_t)n_items + 16));
+  HIPCHK(c, c->walk_scratch.ensure(sizeof(WalkEnt) * walk_cap * n_items + 16));
+  HIPCHK(c, c->mid.ensure(sizeof(uint32_t) * 8 * N_MID32 * n_items + 16));      // SHA-256 | SHA-224 | SHA-1 | MD5 | RIPEMD-160 midstates
+  HIPCHK(c, c->mid64.ensure(sizeof(uint64_t) * 8 * 2 * n_items + 16));   // SHA-512 | SHA-384
+  HIPCHK(c, c->hash_mask.ensure(sizeof(uint32_t) * n_items + 16));
   // partial-length signature packets are linearised into this arena by the parse; the walk reports how much the call needs
   // (mailbox word 2) and a staged call, which does not ask the host in mid-pipeline, lives with the minimum (beyond it: fenced)
   constexpr size_t CHUNK_ARENA_MIN = 64u << 10;
   if (!c->chunk_ctr.p) { HIPCHK(c, c->chunk_ctr.ensure(16)); HIPCHK(c, hipMemsetAsync(c->chunk_ctr.p, 0, 16, c->stream)); }
-  HIPCHK(c, c->chunk_arena.ensure(CHUNK_ARENA_MIN + (staged_cap ? 2 * (size_t)ss_len : 0)));
+  HIPCHK(c, c->chunk_arena.ensure(CHUNK_ARENA_MIN + (call.staged_cap ? 2 * (size_t)call.ss_len : 0)));
   HIPCHK(c, c->pk_count.ensure(sizeof(uint32_t) * PK_COUNT_WORDS));
                                        // [0..3] work-list lengths, [4] some signature uses a hash other than SHA-256,
                                        // [5] some RSA value is too long for the 29-bit form (SIGF_WIDE_VALUE),
                                        // [8..11] lengths after phase 1 (phase 2's start), [12..15] zeros (phase 1's start),
                                        // [16..19] two uint64: clock stamps of k_rsa_modexp (bftkv_gpu_last_sclk_mhz),
                                        // [20..23] DSA class counts (k_dsa_split), [24] k_plan<1>'s ticket (PK_PLAN_TICKET)
-  if (plan_q) HIPCHK(c, c->plan_cut.ensure(sizeof(uint32_t) * (size_t)n_items + 16));
-  TextDev txt{nullptr, nullptr, nullptr, nullptr};
-  if (!d_mid_in) {      // (a midstate-only call cannot hash text-mode signatures: their items come back marked for the ordinary path)
-    HIPCHK(c, c->txt_mid32.ensure(sizeof(uint32_t) * 8 * N_MID32 * (size_t)n_items + 16));
-    HIPCHK(c, c->txt_mid64.ensure(sizeof(uint64_t) * 8 * N_MID64 * (size_t)n_items + 16));
+  if (call.plan_q) HIPCHK(c, c->plan_cut.ensure(sizeof(uint32_t) * n_items + 16));
+  *txt = TextDev{nullptr, nullptr, nullptr, nullptr};
+  if (!call.d_mid_in) {      // (a midstate-only call cannot hash text-mode signatures: their items come back marked for the ordinary path)
+    HIPCHK(c, c->txt_mid32.ensure(sizeof(uint32_t) * 8 * N_MID32 * n_items + 16));
+    HIPCHK(c, c->txt_mid64.ensure(sizeof(uint64_t) * 8 * N_MID64 * n_items + 16));
     HIPCHK(c, c->txt_tail.ensure((size_t)128 * N_HASHES * n_items + 16));
-    HIPCHK(c, c->txt_len.ensure(sizeof(uint64_t) * N_HASHES * (size_t)n_items + 16));
-    txt = TextDev{c->txt_mid32.as<uint32_t>(), c->txt_mid64.as<uint64_t>(), c->txt_tail.as<uint8_t>(), c->txt_len.as<uint64_t>()};
+    HIPCHK(c, c->txt_len.ensure(sizeof(uint64_t) * N_HASHES * n_items + 16));
+    *txt = TextDev{c->txt_mid32.as<uint32_t>(), c->txt_mid64.as<uint64_t>(), c->txt_tail.as<uint8_t>(), c->txt_len.as<uint64_t>()};
   }
-  if (ev_input) HIPCHK(c, hipStreamWaitEvent(s, ev_input, 0));
-  HIPCHK(c, rec(0, s));
-  // the payload midstates do not depend on the parse: start them right away on the hash stream
-  HIPCHK(c, join(sh, 0));
-  HIPCHK(c, rec(5, sh));
-  if (!upload_tbs && !d_mid_in)
-    hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + MID_BLOCK - 1) / MID_BLOCK), dim3(MID_BLOCK), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
-  hipLaunchKernelGGL(k_walk<false>, dim3(n_items), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
-                     (const uint32_t*)nullptr, (SigRec*)nullptr, c->item_flags.as<uint8_t>(), c->walk_scratch.as<WalkEnt>(), walk_cap,
-                     c->chunk_ctr.as<uint32_t>());
-  constexpr uint32_t MAIL_EMPTY = 0xFFFFFFFFu;
-  if (c->h_mail && !staged_cap) __atomic_store_n(&c->h_mail[0], MAIL_EMPTY, __ATOMIC_RELEASE);
-  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, c->counts.as<uint32_t>(), n_items, c->base.as<uint32_t>(),
-                     c->total.as<uint32_t>(), staged_cap ? (uint32_t*)nullptr : c->d_mail, c->pk_count.as<uint32_t>(), c->hash_mask.as<uint32_t>(),
-                     staged_cap, c->chunk_ctr.as<uint32_t>(), staged_cap ? (const uint8_t*)nullptr : c->item_flags.as<uint8_t>(), walk_cap);
-  uint32_t total = staged_cap ? staged_cap : MAIL_EMPTY;      // staged: the upper bound; the kernels read the count from c->total
-  const uint32_t* const n_recs_dev = staged_cap ? c->total.as<uint32_t>() : nullptr;
-  if (c->h_mail && !staged_cap) {
-    // spin on the mailbox (a few microseconds after the scan retires); give up after 20 ms and synchronise
-    const auto t_spin = std::chrono::steady_clock::now();
-    for (uint32_t it = 0;; ++it) {
-      total = __atomic_load_n(&c->h_mail[0], __ATOMIC_ACQUIRE);
-      if (total != MAIL_EMPTY) break;
-      if ((it & 1023u) == 1023u && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(20)) break;
-      __builtin_ia32_pause();
-    }
-  }
-  const bool scan_mailed = c->h_mail && !staged_cap && total != MAIL_EMPTY;
-  uint32_t chunk_units = scan_mailed ? c->h_mail[2] : 0u;
-  const uint32_t overflow_items = scan_mailed ? c->h_mail[plan_report::MAIL_OVERFLOW] : 0u;      // (written ahead of the packet count)
-  if (total == MAIL_EMPTY) {
-    HIPCHK(c, hipMemcpyAsync(&total, c->total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(&chunk_units, c->chunk_ctr.as<uint32_t>() + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-  }
-  if (!staged_cap && (size_t)chunk_units * 16 > c->chunk_arena.cap) HIPCHK(c, c->chunk_arena.ensure((size_t)chunk_units * 16));
-  c->last_total = staged_cap ? 0u : total;      // (per-packet diagnostics are not kept for staged calls)
-  c->last_total_on_dev = staged_cap != 0 && ev_input != nullptr;   // ... a piece's are: its count is read from the device when asked for
-  c->last_items = n_items;
-  c->hb_last_pieces = 0;
-  const size_t tr = total ? total : 1;
+  return 0;
+}
+
+// ... and those sized by the packet count (`tr`: at least 1)
+static int ensure_for_packets(bftkv_gpu_ctx* c, size_t tr) {
   HIPCHK(c, c->recs.ensure(sizeof(SigRec) * tr));
   HIPCHK(c, c->digests.ensure(sizeof(uint32_t) * 16 * tr));
   HIPCHK(c, c->r.ensure(sizeof(uint32_t) * EM_LOW_LIMBS * tr));   // low limbs of s^e mod n: k_rsa_modexp -> k_rsa_compare
@@ -678,41 +645,183 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   if (c->have_rsa4096) HIPCHK(c, c->r4096.ensure(sizeof(uint32_t) * EM_LOW_LIMBS * tr));
   HIPCHK(c, c->dsa_list.ensure(sizeof(uint32_t) * tr));
   if (c->have_dsa_keys) HIPCHK(c, c->dsa_u.ensure(sizeof(uint32_t) * DSA_U_WORDS * tr));
-  if (c->have_dsa3072 && c->have_dsa2048) HIPCHK(c, c->dsa_idx.ensure(sizeof(uint32_t) * 4 * (size_t)tr + 16));      // k_dsa_split: two class lists per phase
-  // A resident big call under a plan sizes what it enqueues from here on by what the device reports (plan_report.h): the scan's
-  // overflow count now, k_plan<1>'s words once the machine-filling modexp is in the queue.  BFTKV_PLAN_REPORT=0: the words are
-  // ignored, and the call is enqueued as every other call is -- grids over `total`, in the order below.
+  if (c->have_dsa3072 && c->have_dsa2048) HIPCHK(c, c->dsa_idx.ensure(sizeof(uint32_t) * 4 * tr + 16));      // k_dsa_split: two class lists per phase
+  return 0;
+}
+
+// What the scan found, for a call that asks the host: from the mailbox, or read back when there is none or it stays empty.
+struct PacketCount { uint32_t total, chunk_units, overflow_items; bool mailed; };
+static int read_packet_count(bftkv_gpu_ctx* c, hipStream_t s, PacketCount* pk) {
+  pk->total = MAIL_EMPTY;
+  if (c->h_mail) {
+    // spin on the mailbox (a few microseconds after the scan retires); give up after 20 ms and synchronise
+    const auto t_spin = std::chrono::steady_clock::now();
+    for (uint32_t it = 0;; ++it) {
+      pk->total = __atomic_load_n(&c->h_mail[0], __ATOMIC_ACQUIRE);
+      if (pk->total != MAIL_EMPTY) break;
+      if ((it & 1023u) == 1023u && std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(20)) break;
+      __builtin_ia32_pause();
+    }
+  }
+  pk->mailed = pk->total != MAIL_EMPTY;
+  if (pk->mailed) {
+    pk->chunk_units = c->h_mail[2];
+    pk->overflow_items = c->h_mail[plan_report::MAIL_OVERFLOW];      // (written ahead of the packet count)
+  } else {
+    HIPCHK(c, hipMemcpyAsync(&pk->total, c->total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(&pk->chunk_units, c->chunk_ctr.as<uint32_t>() + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
+// Wait a moment for k_plan<1>'s flags word (into rin->flags_word; 0: not there at the deadline).  By now the machine-filling
+// modexp is in the queue, so a host that waits for that word delays nothing.
+// lengths_too (a call sized by the report): also for the four list lengths, which the plan's LAST block sends -- under the same
+// deadline.  What that costs: the flags word leaves with the plan's first block, the lengths with its last, so the calling thread
+// spins for the plan's own duration more than it did, and beside a neighbour's modexp, where the plan is starved for block slots,
+// usually to the deadline (cfg 2, three in flight: 0.57 ms per call, the lengths in time in 5 calls of 28; docs/history.md
+// 2026-10-21).  Nothing tells the host sooner that the plan is complete: the lengths are that signal.  The hash stream's work
+// needs the flags word alone: on_flags enqueues it the moment the word is read, or at the deadline without it.
+template <class F>
+static int wait_for_plan_words(bftkv_gpu_ctx* c, uint32_t total, bool lengths_too, plan_report::Input* rin, F&& on_flags) {
+  const auto t_spin = std::chrono::steady_clock::now();
+  bool hashed = false;
+  int rc;
+  for (uint32_t it = 0;; ++it) {
+    const uint32_t v = __atomic_load_n(&c->h_mail[plan_report::MAIL_PLAN_FLAGS], __ATOMIC_ACQUIRE);
+    if (v) {
+      rin->flags_word = v;
+      if (!lengths_too) break;
+      if (!hashed) { if ((rc = on_flags())) return rc; hashed = true; }
+      bool all = true;
+      for (int k = 0; k < plan_report::N_LISTS; ++k) {
+        rin->len_word[k] = __atomic_load_n(&c->h_mail[plan_report::MAIL_LEN0 + k], __ATOMIC_ACQUIRE);
+        all = all && rin->len_word[k] != 0;
+      }
+      if (all) break;
+    }
+    // (the parse and the plan of a big batch take milliseconds themselves: ~0.1 ns per packet each, more beside a neighbour's modexp)
+    if ((it & 255u) == 255u && std::chrono::steady_clock::now() - t_spin > std::chrono::microseconds(300) + std::chrono::nanoseconds((uint64_t)total / 2)) break;
+    __builtin_ia32_pause();
+  }
+  return lengths_too && !hashed ? on_flags() : 0;
+}
+
+// Shared pipeline.  Main stream: walk -> parse -> RSA modexp -> compare.  Hash stream (forked after
+// the parse): SHA-256 midstates -> per-signature digests; joined before the compare.  Leaves SigRec
+// statuses final.
+int run_pipeline(bftkv_gpu_ctx* c, const PipelineCall& call) {
+  const uint32_t n_items = call.n_items, staged_cap = call.staged_cap;
+  const uint8_t* const d_tbs = call.d_tbs; const uint64_t* const d_tbs_off = call.d_tbs_off;
+  const uint8_t* const d_ss = call.d_ss; const uint64_t* const d_ss_off = call.d_ss_off;
+  const uint32_t* const d_mid_in = call.d_mid_in;
+  const QuorumDev* const plan_q = call.plan_q;
+  // What this call is, in one place (`big` and what follows from it: below, once the packet count is known).
+  // staged: sized up front for staged_cap packet events, it never asks the host for its packet count.
+  const bool staged = staged_cap != 0;
+  // A staged small call keeps its hashing on the main stream: its digest kernel is a few microseconds, two cross-stream joins
+  // cost more than that, and a lane that occupies ONE hardware queue leaves the others to the other lanes (the runtime maps
+  // streams onto 4 queues by default: three streams per lane made four lanes run one after the other).
+  // (a capped call that waits for its input on an event is a PIECE of a pipelined host-buffer call: big, so it keeps the side
+  // streams and the turnstile of a resident batch, and like a staged call it never asks the host for its packet count)
+  const bool one_stream = staged && !call.ev_input;
+  // hashes_payloads: the payloads are on the device (or on their way: upload_tbs); false: the caller sent midstates instead
+  const bool hashes_payloads = !d_mid_in;
+  // A staged call with few signatures (no SIMD would get a second wave either way) spreads every <= 2048-bit number over
+  // eight lanes: 0.68x the instructions per wave, and such a call lasts as long as ONE wave's chain of 18 products.
+  static const bool wide8_off = getenv("BFTKV_NO_WIDE8") != nullptr;
+  const bool wide8 = staged && call.ss_len / 256 <= 8192 && !wide8_off;
+  // BFTKV_PLAN_REPORT=0: the device's words are ignored, and a resident big call is enqueued as every other call is
   static const bool report_on = []{ const char* e = getenv("BFTKV_PLAN_REPORT"); return !(e && atoi(e) == 0); }();
-  const bool big = staged_cap ? (ev_input != nullptr && ss_len / 320 >= TURNSTILE_MIN_PACKETS) : total >= TURNSTILE_MIN_PACKETS;
-  const bool report_path = total && plan_q && big && c->h_mail && !staged_cap && !upload_tbs && !d_mid_in;
+  static const bool turnstile_off = getenv("BFTKV_NO_TURNSTILE") != nullptr;      // (read once: this is every big call's path)
+  // s^-1 mod q: one extended GCD per run of signatures under one key (k_dsa_inv_batched) when the DSA work list gives every
+  // key of the ring enough of them (64 on average, 4096 in all: a thread's 16 sorted entries then hold one or two runs), else
+  // one per signature (k_dsa_inv).  The list length lives on the device, so both kernels are enqueued and one of them returns
+  // at once.
+  const size_t n_slots = c->root ? c->n_dsa_slots : c->dsa_comb_slot.size();
+  const uint32_t inv_batch_min = c->dsa_inv_mode == 1 || n_slots > (c->dsa_inv_mode == 2 ? (size_t)INV_MAX_SLOTS : 256) ? 0xFFFFFFFFu
+                                 : c->dsa_inv_mode == 2 ? 0u : (uint32_t)std::max<size_t>(4096, 64 * n_slots);
+
+  hipStream_t s = c->stream, sh = one_stream ? c->stream : c->stream_h;
+  auto rec = [&](int k, hipStream_t st) -> hipError_t { return one_stream ? hipSuccess : hipEventRecord(c->ev[k], st); };
+  auto join = [&](hipStream_t st, int k) -> hipError_t { return one_stream ? hipSuccess : hipStreamWaitEvent(st, c->ev[k], 0); };
+  if (!c->ev[0]) for (auto& e : c->ev) HIPCHK(c, hipEventCreate(&e));
+  // walk scratch row: sized from the average stream length (a packet event needs >= 2 stream bytes, a signature ~100..300);
+  // items with more events than the row holds take the sequential fill pass
+  const uint32_t walk_cap = call.ss_len ? (uint32_t)std::min<uint64_t>(WALK_CAP_MAX, std::max<uint64_t>(WALK_CAP_MIN, call.ss_len / n_items / 48)) : 96u;
+  TextDev txt;
+  int rc;
+  if ((rc = ensure_for_items(c, call, walk_cap, &txt))) return rc;
+  if (call.ev_input) HIPCHK(c, hipStreamWaitEvent(s, call.ev_input, 0));
+  HIPCHK(c, rec(0, s));
+  // the payload midstates do not depend on the parse: start them right away on the hash stream
+  HIPCHK(c, join(sh, 0));
+  HIPCHK(c, rec(5, sh));
+  if (!call.upload_tbs && hashes_payloads)
+    hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + MID_BLOCK - 1) / MID_BLOCK), dim3(MID_BLOCK), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
+  hipLaunchKernelGGL(k_walk<false>, dim3(n_items), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
+                     (const uint32_t*)nullptr, (SigRec*)nullptr, c->item_flags.as<uint8_t>(), c->walk_scratch.as<WalkEnt>(), walk_cap,
+                     c->chunk_ctr.as<uint32_t>());
+  if (c->h_mail && !staged) __atomic_store_n(&c->h_mail[0], MAIL_EMPTY, __ATOMIC_RELEASE);
+  hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, c->counts.as<uint32_t>(), n_items, c->base.as<uint32_t>(),
+                     c->total.as<uint32_t>(), staged ? (uint32_t*)nullptr : c->d_mail, c->pk_count.as<uint32_t>(), c->hash_mask.as<uint32_t>(),
+                     staged_cap, c->chunk_ctr.as<uint32_t>(), staged ? (const uint8_t*)nullptr : c->item_flags.as<uint8_t>(), walk_cap);
+  PacketCount pk{staged_cap, 0u, 0u, false};      // staged: the upper bound; the kernels read the count from c->total
+  if (!staged && (rc = read_packet_count(c, s, &pk))) return rc;
+  const uint32_t total = pk.total;
+  const uint32_t* const n_recs_dev = staged ? c->total.as<uint32_t>() : nullptr;
+  if (!staged && (size_t)pk.chunk_units * 16 > c->chunk_arena.cap) HIPCHK(c, c->chunk_arena.ensure((size_t)pk.chunk_units * 16));
+  c->last_total = staged ? 0u : total;      // (per-packet diagnostics are not kept for staged calls)
+  c->last_total_on_dev = staged && call.ev_input != nullptr;   // ... a piece's are: its count is read from the device when asked for
+  c->last_items = n_items;
+  c->hb_last_pieces = 0;
+  if ((rc = ensure_for_packets(c, total ? total : 1))) return rc;
+  // big: the call's modexp fills the machine, so it takes a turn at the turnstile (a piece is judged by its stream bytes)
+  const bool big = staged ? (call.ev_input != nullptr && call.ss_len / 320 >= TURNSTILE_MIN_PACKETS) : total >= TURNSTILE_MIN_PACKETS;
+  // waits_for_flags: a big call under a plan waits, once its modexp is queued, for the word that says whether any signature
+  // named a hash other than SHA-256
+  const bool waits_for_flags = total && hashes_payloads && plan_q && big && c->h_mail;
+  // report_path: a resident big call under a plan sizes what it enqueues from here on by what the device reports
+  // (plan_report.h): the scan's overflow count now, k_plan<1>'s words once the machine-filling modexp is in the queue; the
+  // diagnostics getter describes such calls.  by_report: ... and the report is on.  Every other call is one with the report
+  // disabled: grids over `total`, in the order below.
+  const bool report_path = waits_for_flags && !staged && !call.upload_tbs;
   const bool by_report = report_path && report_on;
+  // dsa: the call has a DSA side (inverses on their own stream, the table multiplications behind the digests)
+  const bool dsa = total && c->have_dsa_keys;
+
+  // The launch plan: every grid below comes from `dec` (0 blocks: not launched).
   plan_report::Input rin;
   rin.total = total; rin.n_items = n_items; rin.enabled = by_report;
-  rin.overflow_arrived = scan_mailed; rin.overflow_items = overflow_items;
-  rin.wide_form = BFTKV_RSA_FORM == 29; rin.have_rsa3072 = c->have_rsa3072; rin.have_rsa4096 = c->have_rsa4096; rin.have_dsa2048 = c->have_dsa2048; rin.have_dsa3072 = c->have_dsa3072;
+  rin.overflow_arrived = pk.mailed; rin.overflow_items = pk.overflow_items;
+  rin.wide_form = BFTKV_RSA_FORM == 29 && !wide8;
+  rin.have_rsa3072 = c->have_rsa3072; rin.have_rsa4096 = c->have_rsa4096; rin.have_dsa2048 = c->have_dsa2048; rin.have_dsa3072 = c->have_dsa3072;
+  rin.dsa_inv_batched = inv_batch_min != 0xFFFFFFFFu; rin.dsa_inv_single = inv_batch_min != 0u;
   plan_report::Geometry geo;      // (the kernels' own constants: a build with another block size sizes by that)
-  geo.modexp4 = MODEXP_BLOCK / MONT_TPI; geo.modexp8 = MODEXP_BLOCK / MONT_TPI_BIG; geo.compare = 256 / CMP_LANES; geo.dsa_mul = 64;
-  geo.dsa_split = 256; geo.dsa4 = QUADS_PER_BLOCK; geo.dsa8 = RSA_BLOCK / MONT_TPI_BIG; geo.inv_tile = INV_TILE; geo.mid_items = 64;
-  geo.n_hashes = N_HASHES;
+  geo.modexp4 = MODEXP_BLOCK / MONT_TPI; geo.modexp8 = MODEXP_BLOCK / MONT_TPI_BIG; geo.modexp_main = wide8 ? geo.modexp8 : geo.modexp4;
+  geo.compare = 256 / CMP_LANES; geo.dsa_mul = 64; geo.dsa_split = 256; geo.dsa4 = QUADS_PER_BLOCK; geo.dsa8 = RSA_BLOCK / MONT_TPI_BIG;
+  geo.inv_tile = INV_TILE; geo.mid_items = 64; geo.n_hashes = N_HASHES;
   plan_report::Decision dec = plan_report::decide(rin, geo);
   c->have_plan_report = false;
   // fill pass only for items whose event list overflowed the scratch (a no-op grid otherwise; not launched when the scan
   // reported that there are none)
   if (dec.walk_fill)
-    hipLaunchKernelGGL(k_walk<true>, dim3(n_items), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
+    hipLaunchKernelGGL(k_walk<true>, dim3(dec.walk_fill), dim3(64), 0, s, d_ss, d_ss_off, n_items, c->counts.as<uint32_t>(),
                        c->base.as<uint32_t>(), c->recs.as<SigRec>(), c->item_flags.as<uint8_t>(), (WalkEnt*)nullptr, walk_cap, (uint32_t*)nullptr);
   if (total) {
     ParseArgs pa;
     pa.sig_blob = d_ss; pa.sig_off = d_ss_off; pa.rec_base = c->base.as<uint32_t>(); pa.counts = c->counts.as<uint32_t>(); pa.n_items = n_items;
-    pa.scratch = c->walk_scratch.as<WalkEnt>(); pa.walk_cap = walk_cap; pa.recs = c->recs.as<SigRec>(); pa.n_recs = total; pa.cert_ent = d_cert_ent;
+    pa.scratch = c->walk_scratch.as<WalkEnt>(); pa.walk_cap = walk_cap; pa.recs = c->recs.as<SigRec>(); pa.n_recs = total; pa.cert_ent = call.d_cert_ent;
     pa.pk_list = c->pk_list.as<uint32_t>(); pa.pk_list3072 = c->pk_list3072.as<uint32_t>(); pa.pk_list4096 = c->pk_list4096.as<uint32_t>();
     pa.pk_count = c->pk_count.as<uint32_t>(); pa.dsa_list = c->dsa_list.as<uint32_t>(); pa.item_hash_mask = c->hash_mask.as<uint32_t>();
-    pa.sig_class = d_sig_class; pa.forced_issuer = d_forced_issuer; pa.msg_slot = d_msg_slot; pa.msg_hash = d_msg_hash; pa.item_flags = c->item_flags.as<uint8_t>();
+    pa.sig_class = call.d_sig_class; pa.forced_issuer = call.d_forced_issuer; pa.msg_slot = call.d_msg_slot; pa.msg_hash = call.d_msg_hash;
+    pa.item_flags = c->item_flags.as<uint8_t>();
     pa.defer_queue = plan_q ? 1u : 0u;
     pa.n_recs_dev = n_recs_dev;
     pa.chunk_arena = c->chunk_arena.as<uint8_t>(); pa.chunk_cap_units = (uint32_t)std::min<size_t>(c->chunk_arena.cap / 16, 0xFFFFFFF0u);
     pa.chunk_bump = c->chunk_ctr.as<uint32_t>() + 1;
-    if (!staged_cap && (uint64_t)total >= 128ull * n_items)     // very long items (n = 256 cliques: 171+ packets): block per item, no bisection
+    if (!staged && (uint64_t)total >= 128ull * n_items)     // very long items (n = 256 cliques: 171+ packets): block per item, no bisection
                                                  // (measured at 53 packets per item: 237 us item-major vs 210 us record-major)
       hipLaunchKernelGGL(k_parse_body_items, dim3(n_items), dim3(PARSE_ITEM_BLOCK), 0, s, pa, c->kt);
     else
@@ -720,6 +829,7 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
   }
   uint32_t* const cnt_p = c->pk_count.as<uint32_t>();
   const uint32_t* const start0 = cnt_p + 12;        // phase 1 starts every work list at 0
+  const uint32_t* const start1 = cnt_p + 8;         // phase 2: at the lengths after phase 1
   PlanArgs pl{};
   if (total && plan_q) {
     pl.recs = c->recs.as<SigRec>(); pl.rec_base = c->base.as<uint32_t>(); pl.counts = c->counts.as<uint32_t>(); pl.n_items = n_items;
@@ -735,26 +845,18 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     }
     hipLaunchKernelGGL(k_plan<1>, dim3((n_items + PLAN_ITEMS - 1) / PLAN_ITEMS), dim3(PLAN_BLOCK), 0, s, pl, c->kt, *plan_q);
   }
-  const bool dsa_side = total && c->have_dsa_keys;
-  if (one_stream && dsa_side) HIPCHK(c, hipEventRecord(c->ev[1], s)); else HIPCHK(c, rec(1, s));
-  // s^-1 mod q: one extended GCD per run of signatures under one key (k_dsa_inv_batched) when the DSA work list gives every
-  // key of the ring enough of them (64 on average, 4096 in all: a thread's 16 sorted entries then hold one or two runs), else
-  // one per signature (k_dsa_inv).  The list length lives on the device, so both kernels are enqueued and one of them returns
-  // at once.
-  const size_t n_slots = c->root ? c->n_dsa_slots : c->dsa_comb_slot.size();
-  const uint32_t inv_batch_min = c->dsa_inv_mode == 1 || n_slots > (c->dsa_inv_mode == 2 ? (size_t)INV_MAX_SLOTS : 256) ? 0xFFFFFFFFu
-                                 : c->dsa_inv_mode == 2 ? 0u : (uint32_t)std::max<size_t>(4096, 64 * n_slots);
-  auto launch_dsa_inv = [&](hipStream_t st, const uint32_t* start, uint32_t bound /* of the entries behind `start` */) {
-    if (inv_batch_min != 0xFFFFFFFFu)
-      hipLaunchKernelGGL(k_dsa_inv_batched, dim3((bound + INV_TILE - 1) / INV_TILE), dim3(INV_BLOCK), 0, st, d_ss, c->recs.as<SigRec>(),
+  if (one_stream && dsa) HIPCHK(c, hipEventRecord(c->ev[1], s)); else HIPCHK(c, rec(1, s));
+  auto launch_dsa_inv = [&](hipStream_t st, const uint32_t* start, const plan_report::PhaseGrids& pg) {
+    if (pg.dsa_inv_batched)
+      hipLaunchKernelGGL(k_dsa_inv_batched, dim3(pg.dsa_inv_batched), dim3(INV_BLOCK), 0, st, d_ss, c->recs.as<SigRec>(),
                          c->dsa_list.as<uint32_t>(), c->pk_count.as<uint32_t>(), start, c->kt, c->dsa_u.as<uint32_t>(), inv_batch_min);
-    if (inv_batch_min != 0u)
-      hipLaunchKernelGGL(k_dsa_inv, dim3((bound + 63) / 64), dim3(64), 0, st, d_ss, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(),
+    if (pg.dsa_inv)
+      hipLaunchKernelGGL(k_dsa_inv, dim3(pg.dsa_inv), dim3(64), 0, st, d_ss, c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(),
                          c->pk_count.as<uint32_t>(), start, c->kt, c->dsa_u.as<uint32_t>(), inv_batch_min);
   };
-  if (total && c->have_dsa_keys) {
+  if (dsa) {
     HIPCHK(c, hipStreamWaitEvent(c->stream_d, c->ev[1], 0));
-    launch_dsa_inv(c->stream_d, start0, total);
+    launch_dsa_inv(c->stream_d, start0, dec.p1);
     HIPCHK(c, hipEventRecord(c->ev[7], c->stream_d));
   }
   auto hash_stream_work = [&]() -> int {
@@ -762,60 +864,56 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     HIPCHK(c, join(sh, 1));
     if (total) {
       // other hashes: a no-op grid unless some signature asked for them (not launched when the plan reported that none did)
-      if (!d_mid_in && dec.mid_other) {
-        hipLaunchKernelGGL(k_hash_mid_other, dim3((n_items + 63) / 64, N_HASHES - 1), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items,
+      if (hashes_payloads && dec.mid_other) {
+        hipLaunchKernelGGL(k_hash_mid_other, dim3(dec.mid_x, geo.n_hashes - 1), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items,
                            c->hash_mask.as<uint32_t>(), c->mid.as<uint32_t>(), c->mid64.as<uint64_t>());
-        hipLaunchKernelGGL(k_hash_mid_text, dim3((n_items + 63) / 64, N_HASHES), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items, c->hash_mask.as<uint32_t>(), txt);
+        hipLaunchKernelGGL(k_hash_mid_text, dim3(dec.mid_x, geo.n_hashes), dim3(64), 0, sh, d_tbs, d_tbs_off, n_items, c->hash_mask.as<uint32_t>(), txt);
       }
       hipLaunchKernelGGL(k_digest_sha256, dim3((total + 255) / 256), dim3(256), 0, sh, d_tbs, d_tbs_off, d_ss,
                          d_mid_in ? d_mid_in : c->mid.as<uint32_t>(), c->mid64.as<uint64_t>(), n_items, c->recs.as<SigRec>(), total,
-                         c->digests.as<uint32_t>(), d_tbs_prefix, n_recs_dev);
+                         c->digests.as<uint32_t>(), call.d_tbs_prefix, n_recs_dev);
     }
     HIPCHK(c, rec(6, sh));
     return 0;
   };
   // (by the report: behind the wait for the plan's words below -- this work waits for the plan on the device anyway)
-  if (!upload_tbs && !by_report) { int hrc = hash_stream_work(); if (hrc) return hrc; }
+  if (!call.upload_tbs && !by_report && (rc = hash_stream_work())) return rc;
   // main stream: modular exponentiations (status bytes are only written by the hash stream meanwhile)
-  const dim3 qg((total + MODEXP_BLOCK / MONT_TPI - 1) / (MODEXP_BLOCK / MONT_TPI));
-  const dim3 qg8((total + MODEXP_BLOCK / MONT_TPI_BIG - 1) / (MODEXP_BLOCK / MONT_TPI_BIG));   // 8 lanes per number
-  // A staged call with few signatures (no SIMD would get a second wave either way) spreads every <= 2048-bit number over
-  // eight lanes: 0.68x the instructions per wave, and such a call lasts as long as ONE wave's chain of 18 products.
-  static const bool wide8_off = getenv("BFTKV_NO_WIDE8") != nullptr;
-  const bool wide8 = staged_cap != 0 && ss_len / 256 <= 8192 && !wide8_off;
-  struct ModexpGrids { uint32_t main, wide, m3072, m4096; };      // blocks per launch, 0: not launched
-  const ModexpGrids mg_total{wide8 ? qg8.x : qg.x, qg.x, c->have_rsa3072 ? qg8.x : 0u, c->have_rsa4096 ? qg8.x : 0u};
-  auto launch_modexp = [&](const uint32_t* start, const ModexpGrids& mg) {
-    if (wide8) {
-      if (mg.main)
-        hipLaunchKernelGGL((k_rsa_modexp<10, MONT_TPI_BIG>), dim3(mg.main), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
-    } else {
+  // the 19 x 4 form of 28 bits for the values too long for 72 limbs (262 .. 266 bytes; k_parse_body flags them and raises
+  // cnt_p[5]): normally a grid of blocks that read one word and return
+  auto launch_wide = [&](const uint32_t* start, uint32_t blocks) {
 #if BFTKV_RSA_FORM == 29
-      // 18 x 4 limbs of 29 bits (2 x 64 x 72 x 4 B of LDS per block), and right behind it the 19 x 4 form of 28 bits for the
-      // values too long for 72 limbs (262 .. 266 bytes; k_parse_body flags them and raises cnt_p[5]): normally a grid of
-      // blocks that read one word and return
-      if (mg.main)
-        hipLaunchKernelGGL((k_rsa_modexp<RSA29_L, MONT_TPI, RSA29_W>), dim3(mg.main), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16), (const uint32_t*)(cnt_p + 5));
-      if (mg.wide)
-        hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI, MONT_W, true>), dim3(mg.wide), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr, (const uint32_t*)(cnt_p + 5));
+    if (blocks)
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI, MONT_W, true>), dim3(blocks), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr, (const uint32_t*)(cnt_p + 5));
 #else
-      if (mg.main)
-        hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI>), dim3(mg.main), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
-                           cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
+    (void)start; (void)blocks;      // (never sized: Input::wide_form is false)
+#endif
+  };
+  // wide_inline: the pass over the long values right behind the main pass, as every call has it but the one sized by the report
+  auto launch_modexp = [&](const uint32_t* start, const plan_report::PhaseGrids& pg, bool wide_inline) {
+    if (pg.modexp && wide8) {
+      hipLaunchKernelGGL((k_rsa_modexp<10, MONT_TPI_BIG>), dim3(pg.modexp), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
+    } else if (pg.modexp) {
+#if BFTKV_RSA_FORM == 29
+      // 18 x 4 limbs of 29 bits (2 x 64 x 72 x 4 B of LDS per block)
+      hipLaunchKernelGGL((k_rsa_modexp<RSA29_L, MONT_TPI, RSA29_W>), dim3(pg.modexp), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16), (const uint32_t*)(cnt_p + 5));
+#else
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L, MONT_TPI>), dim3(pg.modexp), dim3(MODEXP_BLOCK), c->modexp_lds_pad, s, d_ss, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
+                         cnt_p, start, c->kt, c->r.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)(cnt_p + 16));
 #endif
     }
+    if (wide_inline) launch_wide(start, pg.wide);
     // larger moduli: only when the keyring holds such keys (blocks beyond the queued count exit at once)
-    if (mg.m3072)
-      hipLaunchKernelGGL((k_rsa_modexp<MONT_L3072, MONT_TPI_BIG>), dim3(mg.m3072), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
+    if (pg.modexp3072)
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L3072, MONT_TPI_BIG>), dim3(pg.modexp3072), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list3072.as<uint32_t>(),
                          cnt_p + 2, start + 2, c->kt, c->r3072.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr);
-    if (mg.m4096)
-      hipLaunchKernelGGL((k_rsa_modexp<MONT_L4096, MONT_TPI_BIG>), dim3(mg.m4096), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list4096.as<uint32_t>(),
+    if (pg.modexp4096)
+      hipLaunchKernelGGL((k_rsa_modexp<MONT_L4096, MONT_TPI_BIG>), dim3(pg.modexp4096), dim3(MODEXP_BLOCK), 0, s, d_ss, c->recs.as<SigRec>(), c->pk_list4096.as<uint32_t>(),
                          cnt_p + 3, start + 3, c->kt, c->r4096.as<uint32_t>(), c->xr.as<uint32_t>(), (uint64_t*)nullptr);
   };
-  static const bool turnstile_off = getenv("BFTKV_NO_TURNSTILE") != nullptr;      // (read once: this is every big call's path)
   // a launch that fills the machine takes its turn behind the modexp of whichever context went last
   auto at_turnstile = [&](const std::function<void()>& launch, bool stamp) -> hipError_t {
     Turnstile& g = g_turnstile[(unsigned)c->device & 15u];
@@ -829,100 +927,55 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     g.last = c->ev_turn; g.owner = c;
     return hipSuccess;
   };
-  // by the report: the pass over the values too long for the 29-bit form waits for the plan's word, behind the wait below
-  ModexpGrids mg1 = mg_total;
-  if (by_report) mg1.wide = 0;
+  // By the report, the pass over the long values waits for the flags word and goes apart from the main pass.  With the bit
+  // read, it fills the machine as any modexp does and takes a turn at the turnstile of its own: this call's compare and phase 2
+  // then stand behind the neighbour's modexp that went in between, and the call publishes a new turn.  With no flags word at the
+  // deadline the grid is the one it always was, normally empty, and goes straight behind this call's modexp on the stream
+  // WITHOUT a turn: the parent had it inside the main modexp's turn, so here a neighbour admitted after that turn may run
+  // beside it.  (Either way it lies behind event 2: bftkv_gpu_last_timing's modexp figure does not include it.)
+  auto launch_wide_apart = [&](const uint32_t* start, uint32_t blocks) -> hipError_t {
+    if (blocks && !turnstile_off && dec.flags_used) return at_turnstile([&] { launch_wide(start, blocks); }, false);
+    launch_wide(start, blocks);
+    return hipSuccess;
+  };
   if (big && !turnstile_off) {
-    HIPCHK(c, at_turnstile([&] { launch_modexp(start0, mg1); }, true));
+    HIPCHK(c, at_turnstile([&] { launch_modexp(start0, dec.p1, !by_report); }, true));
   } else {
     HIPCHK(c, rec(9, s));
-    if (total) launch_modexp(start0, mg1);
+    launch_modexp(start0, dec.p1, !by_report);
   }
   HIPCHK(c, rec(2, s));
-  if (upload_tbs) {
-    int hrc = (*upload_tbs)(sh);
-    if (hrc) return hrc;
-    if (!mid_prelaunched)
+  if (call.upload_tbs) {
+    if ((rc = (*call.upload_tbs)(sh))) return rc;
+    if (!call.mid_prelaunched)
       hipLaunchKernelGGL(k_sha256_mid, dim3((n_items + MID_BLOCK - 1) / MID_BLOCK), dim3(MID_BLOCK), 0, sh, d_tbs, d_tbs_off, n_items, c->mid.as<uint32_t>());
-    if ((hrc = hash_stream_work())) return hrc;
+    if ((rc = hash_stream_work())) return rc;
   }
   if (!by_report) HIPCHK(c, join(s, 6));
-  // digests of the hashes other than SHA-256: on the MAIN stream, after the modexp.  Normally there are none and the kernel
-  // exits on a device-side flag; at its 203 VGPRs it cannot co-schedule beside k_rsa_modexp, and on the hash stream it sat
-  // there until the modexp drained (1.7 ms per step in the trace) holding back the join.
-  // ... and normally not even launched: k_plan<1> reports through the mailbox whether any signature named another hash; by now
-  // the machine-filling modexp is in the queue, so a host that waits a moment for that word delays nothing.  (A profile of the
-  // step used to show this no-op as the kernel that "ran" while a neighbour's modexp held the SIMDs.)
-  bool other_hashes = true;
-  if (total && !d_mid_in && plan_q && big && c->h_mail) {
-    const auto t_spin = std::chrono::steady_clock::now();
-    // by the report: also for the four list lengths, which the plan's LAST block sends -- under the same deadline.  What that
-    // costs: the flags word leaves with the plan's first block, the lengths with its last, so the calling thread spins for the
-    // plan's own duration more than it did, and beside a neighbour's modexp, where the plan is starved for block slots, usually
-    // to the deadline (cfg 2, three in flight: 0.57 ms per call, the lengths in time in 5 calls of 28; docs/history.md
-    // 2026-10-21).  Nothing tells the host sooner that the plan is complete: the lengths are that signal.  The hash stream's
-    // work needs the flags word alone and is enqueued the moment it is read.
-    bool hashed = false;
-    for (uint32_t it = 0;; ++it) {
-      const uint32_t v = __atomic_load_n(&c->h_mail[plan_report::MAIL_PLAN_FLAGS], __ATOMIC_ACQUIRE);
-      if (v) {
-        other_hashes = (v & plan_report::FLAG_OTHER_HASH) != 0;
-        rin.flags_word = v;
-        if (!by_report) break;
-        if (!hashed) {
-          dec = plan_report::decide(rin, geo);      // (for the midstates of the other hashes: the flags are all they depend on)
-          int hrc = hash_stream_work(); if (hrc) return hrc;
-          hashed = true;
-        }
-        bool all = true;
-        for (int k = 0; k < plan_report::N_LISTS; ++k) {
-          rin.len_word[k] = __atomic_load_n(&c->h_mail[plan_report::MAIL_LEN0 + k], __ATOMIC_ACQUIRE);
-          all = all && rin.len_word[k] != 0;
-        }
-        if (all) break;
-      }
-      // (the parse and the plan of a big batch take milliseconds themselves: ~0.1 ns per packet each, more beside a neighbour's modexp)
-      if ((it & 255u) == 255u && std::chrono::steady_clock::now() - t_spin > std::chrono::microseconds(300) + std::chrono::nanoseconds((uint64_t)total / 2)) break;
-      __builtin_ia32_pause();
-    }
-    if (by_report && !hashed) { int hrc = hash_stream_work(); if (hrc) return hrc; }      // (no flags word: `dec` still says "launch them")
-  }
-  rin.dsa_inv_batched = inv_batch_min != 0xFFFFFFFFu; rin.dsa_inv_single = inv_batch_min != 0u;
-  if (report_path) {
-    dec = plan_report::decide(rin, geo);
+  if (waits_for_flags &&
+      (rc = wait_for_plan_words(c, total, by_report, &rin, [&]() -> int {
+         dec = plan_report::decide(rin, geo);      // (for the midstates of the other hashes: the flags are all they depend on)
+         return hash_stream_work();
+       }))) return rc;
+  if (by_report) dec = plan_report::decide(rin, geo);      // (off the report no word changes a grid)
+  if (report_path) {      // the getter flattens exactly the numbers the launches above and below read
     plan_report::flatten(dec, rin, c->last_plan_report);
     c->have_plan_report = true;
   }
   if (by_report) {
-    // The pass over the long values waited for the flags word.  With the bit read, it fills the machine as any modexp does and
-    // takes a turn at the turnstile of its own: this call's compare and phase 2 then stand behind the neighbour's modexp that
-    // went in between, and the call publishes a new turn.  With no flags word at the deadline the grid is the one it always was,
-    // normally empty, and goes straight behind this call's modexp on the stream WITHOUT a turn: the parent had it inside the
-    // main modexp's turn, so here a neighbour admitted after that turn may run beside it.  (Either way it lies behind event 2:
-    // bftkv_gpu_last_timing's modexp figure does not include it.)
-    const ModexpGrids mgw{0u, dec.p1.wide, 0u, 0u};
-    if (mgw.wide) {
-      if (!turnstile_off && dec.flags_used) HIPCHK(c, at_turnstile([&] { launch_modexp(start0, mgw); }, false));
-      else launch_modexp(start0, mgw);
-    }
+    HIPCHK(c, launch_wide_apart(start0, dec.p1.wide));
     HIPCHK(c, join(s, 6));
   }
-  if (total && !d_mid_in && other_hashes)
+  // digests of the hashes other than SHA-256: on the MAIN stream, after the modexp.  Normally there are none and the kernel
+  // exits on a device-side flag; at its 203 VGPRs it cannot co-schedule beside k_rsa_modexp, and on the hash stream it sat
+  // there until the modexp drained (1.7 ms per step in the trace) holding back the join.
+  // ... and normally not even launched: the flags word says whether any signature named another hash.  (A profile of the
+  // step used to show this no-op as the kernel that "ran" while a neighbour's modexp held the SIMDs.)
+  const bool other_hashes = rin.flags_word ? (rin.flags_word & plan_report::FLAG_OTHER_HASH) != 0 : true;
+  if (total && hashes_payloads && other_hashes)
     hipLaunchKernelGGL(k_digest_other, dim3(std::min<uint32_t>((total + 255) / 256, DIGEST_OTHER_MAX_BLOCKS)), dim3(256), 0, s,
                        d_tbs, d_tbs_off, d_ss, c->mid.as<uint32_t>(), c->mid64.as<uint64_t>(), n_items, c->recs.as<SigRec>(), total,
                        c->digests.as<uint32_t>(), c->pk_count.as<uint32_t>() + 4, txt, n_recs_dev);
-  // grids of a phase: over `total` as ever (blocks beyond the device-side count exit at once), or -- the resident big call --
-  // over what the plan reported
-  const uint32_t cg = (uint32_t)(((uint64_t)total * CMP_LANES + 255) / 256);
-  plan_report::PhaseGrids pg_total;
-  pg_total.compare[plan_report::L_RSA2048] = cg;
-  pg_total.compare[plan_report::L_RSA3072] = c->have_rsa3072 ? cg : 0u;
-  pg_total.compare[plan_report::L_RSA4096] = c->have_rsa4096 ? cg : 0u;
-  pg_total.dsa_mul = (total + 63) / 64; pg_total.dsa_split = c->have_dsa3072 && c->have_dsa2048 ? (total + 255) / 256 : 0u;
-  pg_total.dsa_modexp4 = c->have_dsa2048 ? (total + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK : 0u;
-  pg_total.dsa_modexp8 = c->have_dsa3072 ? (total + RSA_BLOCK / MONT_TPI_BIG - 1) / (RSA_BLOCK / MONT_TPI_BIG) : 0u;
-  const plan_report::PhaseGrids& pg1 = report_path ? dec.p1 : pg_total;
-  const plan_report::PhaseGrids& pg2 = report_path ? dec.p2 : pg_total;
   auto launch_compare = [&](const uint32_t* start, const plan_report::PhaseGrids& pg) {
     if (pg.compare[plan_report::L_RSA2048])
       hipLaunchKernelGGL(k_rsa_compare, dim3(pg.compare[plan_report::L_RSA2048]), dim3(256), 0, s, c->recs.as<SigRec>(), c->pk_list.as<uint32_t>(),
@@ -960,14 +1013,15 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
       hipLaunchKernelGGL((k_dsa_modexp<MONT_L3072, MONT_TPI_BIG>), dim3(pg.dsa_modexp8), dim3(RSA_BLOCK), 0, s,
                          c->recs.as<SigRec>(), c->dsa_list.as<uint32_t>(), cnt_p, start, c->kt, c->dsa_u.as<uint32_t>(), idx_b, cnt_cls ? cnt_cls + 1 : nullptr);
   };
-  if (total) launch_compare(start0, pg1);
+  launch_compare(start0, dec.p1);
   HIPCHK(c, rec(8, s));
-  if (total && c->have_dsa_keys) {
+  if (dsa) {
     HIPCHK(c, hipStreamWaitEvent(s, c->ev[7], 0));
-    launch_dsa(start0, pg1);
+    launch_dsa(start0, dec.p1);
   }
   if (total && plan_q) {
-    // phase 2: tally what phase 1 verified; whatever an item still lacks comes from its remaining packets
+    // phase 2: tally what phase 1 verified; whatever an item still lacks comes from its remaining packets.  No list can grow by
+    // more than the packets phase 1 left unqueued (dec.phase2_bound; `total` without the plan's words)
     HIPCHK(c, c->o_nver.ensure(sizeof(uint32_t) * n_items));
     HIPCHK(c, c->o_verdict.ensure(n_items));
     hipLaunchKernelGGL(k_tally, dim3((n_items + 3) / 4), dim3(256), 0, s, c->recs.as<SigRec>(), c->base.as<uint32_t>(), c->counts.as<uint32_t>(),
@@ -975,29 +1029,17 @@ int run_pipeline(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t* d_tbs, const
     hipLaunchKernelGGL(k_plan_snapshot, dim3(1), dim3(64), 0, s, cnt_p);
     pl.verdict = c->o_verdict.as<uint8_t>();
     hipLaunchKernelGGL(k_plan<2>, dim3((n_items + PLAN_ITEMS - 1) / PLAN_ITEMS), dim3(PLAN_BLOCK), 0, s, pl, c->kt, *plan_q);
-    const uint32_t* const start1 = cnt_p + 8;
-    if (!by_report) {
-      if (c->have_dsa_keys) launch_dsa_inv(s, start1, total);
-      launch_modexp(start1, mg_total);
-    } else {
-      // no list can grow by more than the packets phase 1 left unqueued (dec.phase2_bound; `total` without the plan's words)
-      if (c->have_dsa_keys && dec.phase2_bound) launch_dsa_inv(s, start1, dec.phase2_bound);
-      launch_modexp(start1, ModexpGrids{dec.modexp2, 0u, dec.modexp2_3072, dec.modexp2_4096});
-      // (the long values: behind a turn at the turnstile when this call sizes by the report, as in phase 1)
-      const ModexpGrids mgw{0u, dec.p2.wide, 0u, 0u};
-      if (mgw.wide) {
-        if (!turnstile_off && dec.flags_used) HIPCHK(c, at_turnstile([&] { launch_modexp(start1, mgw); }, false));
-        else launch_modexp(start1, mgw);
-      }
-    }
-    launch_compare(start1, pg2);
-    if (c->have_dsa_keys) launch_dsa(start1, pg2);
+    launch_dsa_inv(s, start1, dec.p2);
+    launch_modexp(start1, dec.p2, !by_report);
+    if (by_report) HIPCHK(c, launch_wide_apart(start1, dec.p2.wide));      // (behind a turn of its own, as in phase 1)
+    launch_compare(start1, dec.p2);
+    launch_dsa(start1, dec.p2);
   }
   // several keys under one key id: what the candidates behind the first do to the status of a record it did not verify
   // (never to a verdict: see the kernel)
-  if (total && c->have_ambiguous && !d_msg_slot)
+  if (total && c->have_ambiguous && !call.d_msg_slot)
     hipLaunchKernelGGL(k_candidates, dim3((total + 63) / 64), dim3(64), 0, s, d_tbs, d_tbs_off, d_ss, d_mid_in ? d_mid_in : c->mid.as<uint32_t>(),
-                       c->mid64.as<uint64_t>(), n_items, c->recs.as<SigRec>(), total, n_recs_dev, d_tbs_prefix, c->kt, d_cert_ent, d_sig_class, txt,
+                       c->mid64.as<uint64_t>(), n_items, c->recs.as<SigRec>(), total, n_recs_dev, call.d_tbs_prefix, c->kt, call.d_cert_ent, call.d_sig_class, txt,
                        c->hash_mask.as<uint32_t>());
   HIPCHK(c, rec(3, s));
   HIPCHK(c, hipGetLastError());
@@ -1728,11 +1770,11 @@ int bftkv_gpu_quorum_destroy(bftkv_gpu_ctx* c, int quorum) {
   return 0;
 }
 
-static int collective_verify_impl(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off,
-                                  const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
-                                  uint8_t* verdict_out, uint8_t* fenced_out, const std::function<int(hipStream_t)>* upload_tbs, uint64_t ss_len,
-                                  hipEvent_t ev_input = nullptr, uint32_t cap = 0, bool mid_prelaunched = false) {
+// `call`: the batch and how it arrives, as the caller prepared it; the plan (call.plan_q) is set here
+static int collective_verify_impl(bftkv_gpu_ctx* c, int quorum, PipelineCall call, uint8_t* err_out, uint32_t* nver_out,
+                                  uint8_t* verdict_out, uint8_t* fenced_out) {
   // caller holds c->mu
+  const uint32_t n_items = call.n_items;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = check_quorum(c, quorum);
   if (rc) return rc;
@@ -1740,7 +1782,8 @@ static int collective_verify_impl(bftkv_gpu_ctx* c, int quorum, uint32_t n_items
   QuorumHost& q = c->quorums[quorum];
   if ((rc = build_member(c, q))) return rc;
   const QuorumDev qd = quorum_dev(c, q);
-  if ((rc = run_pipeline(c, n_items, tbs, tbs_off, ss, ss_off, nullptr, nullptr, nullptr, nullptr, upload_tbs, c->early_exit ? &qd : nullptr, ss_len, nullptr, nullptr, cap, ev_input, mid_prelaunched))) return rc;
+  call.plan_q = c->early_exit ? &qd : nullptr;
+  if ((rc = run_pipeline(c, call))) return rc;
   HIPCHK(c, c->o_nver.ensure(sizeof(uint32_t) * n_items));
   HIPCHK(c, c->o_verdict.ensure(n_items));
   uint32_t* nv = nver_out ? nver_out : c->o_nver.as<uint32_t>();
@@ -1767,7 +1810,9 @@ int bftkv_gpu_collective_verify_dev(bftkv_gpu_ctx* c, int quorum, uint32_t n_ite
   ctx_lock lk(c->mu);
   KtRead kr(c);
   if (kr.rc) return kr.rc;
-  return collective_verify_impl(c, quorum, n_items, tbs, tbs_off, ss, ss_off, err_out, nver_out, verdict_out, fenced_out, nullptr, ss_len);
+  PipelineCall call;
+  call.n_items = n_items; call.d_tbs = tbs; call.d_tbs_off = tbs_off; call.d_ss = ss; call.d_ss_off = ss_off; call.ss_len = ss_len;
+  return collective_verify_impl(c, quorum, call, err_out, nver_out, verdict_out, fenced_out);
 }
 
 // A big batch handed over in HOST memory (what the cgo shim and every C caller do: crypto_pgp.go:485-500, the caller owns
@@ -1786,6 +1831,14 @@ int bftkv_gpu_collective_verify_dev(bftkv_gpu_ctx* c, int quorum, uint32_t n_ite
 // Items are independent, so the verdicts are those of the unsplit call by construction (test_host_buffer_pipeline_*).
 
 struct HbPiece { uint32_t i0, i1; };
+
+// fail closed: no byte of the caller's result arrays reads as "verified" beside a non-zero return code
+static void fail_closed(uint32_t n_items, uint8_t* err_out, uint32_t* nver_out, uint8_t* verdict_out, uint8_t* fenced_out) {
+  if (err_out) memset(err_out, BFTKV_ERR_INSUFFICIENT_SIGNATURES, n_items);
+  if (verdict_out) memset(verdict_out, 0, n_items);
+  if (nver_out) memset(nver_out, 0, sizeof(uint32_t) * (size_t)n_items);
+  if (fenced_out) memset(fenced_out, 0, n_items);
+}
 
 // Segmented payloads (bftkv_gpu_collective_verify_segments): payload i = prefix[prefix_off[i] .. prefix_off[i+1]) || shared segment
 // seg[i] (0xFFFFFFFF: none).  Only the prefixes and each distinct segment cross PCIe; k_expand_segments lays the payloads out in
@@ -2124,9 +2177,11 @@ static int collective_verify_pipelined(bftkv_gpu_ctx* c, int quorum, uint32_t n_
     const uint32_t cap = !use_cap ? 0u
                          : c->hb_tight ? (uint32_t)(ssk / 4096 + 1)       // (tests: a bound that real streams exceed, to exercise the second pass)
                                        : (uint32_t)std::min<uint64_t>(1u << 26, ssk / 64 + 8ull * nk + 4096);
-    rc = collective_verify_impl(w, quorum, nk, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>() + pc[k].i0, c->in_ss.as<uint8_t>(),
-                                c->in_ss_off.as<uint64_t>() + pc[k].i0, w->o_err.as<uint8_t>(), nullptr, nullptr,
-                                fenced_out ? w->o_fenced.as<uint8_t>() : nullptr, &payload_ready, ssk, c->hb_ev[2 * k], cap, early_mids && k > 0);
+    PipelineCall piece;
+    piece.n_items = nk; piece.d_tbs = c->in_tbs.as<uint8_t>(); piece.d_tbs_off = c->in_tbs_off.as<uint64_t>() + pc[k].i0;
+    piece.d_ss = c->in_ss.as<uint8_t>(); piece.d_ss_off = c->in_ss_off.as<uint64_t>() + pc[k].i0; piece.ss_len = ssk;
+    piece.upload_tbs = &payload_ready; piece.ev_input = c->hb_ev[2 * k]; piece.staged_cap = cap; piece.mid_prelaunched = early_mids && k > 0;
+    rc = collective_verify_impl(w, quorum, piece, w->o_err.as<uint8_t>(), nullptr, nullptr, fenced_out ? w->o_fenced.as<uint8_t>() : nullptr);
     ++launched;
     if (rc) { c->err = "host-buffer pipeline, piece " + std::to_string(k) + ": " + w->err; first_rc = rc; break; }
     const uint32_t i0 = pc[k].i0;
@@ -2161,9 +2216,10 @@ static int collective_verify_pipelined(bftkv_gpu_ctx* c, int quorum, uint32_t n_
     if (!use_cap || !tot[1]) continue;
     ctx_lock wl(w->mu);
     const uint32_t nk = pc[k].i1 - pc[k].i0, i0 = pc[k].i0;
-    rc = collective_verify_impl(w, quorum, nk, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>() + i0, c->in_ss.as<uint8_t>(),
-                                c->in_ss_off.as<uint64_t>() + i0, w->o_err.as<uint8_t>(), nullptr, nullptr,
-                                fenced_out ? w->o_fenced.as<uint8_t>() : nullptr, nullptr, ss_off[pc[k].i1] - ss_off[i0]);
+    PipelineCall piece;      // (its input is on the device: a resident call)
+    piece.n_items = nk; piece.d_tbs = c->in_tbs.as<uint8_t>(); piece.d_tbs_off = c->in_tbs_off.as<uint64_t>() + i0;
+    piece.d_ss = c->in_ss.as<uint8_t>(); piece.d_ss_off = c->in_ss_off.as<uint64_t>() + i0; piece.ss_len = ss_off[pc[k].i1] - ss_off[i0];
+    rc = collective_verify_impl(w, quorum, piece, w->o_err.as<uint8_t>(), nullptr, nullptr, fenced_out ? w->o_fenced.as<uint8_t>() : nullptr);
     hipError_t e = hipSuccess;
     if (rc) { c->err = "host-buffer pipeline, piece " + std::to_string(k) + " (second pass): " + w->err; first_rc = rc; break; }
     if ((e = hipMemcpyAsync(c->hb_out + o_err + i0, w->o_err.p, nk, hipMemcpyDeviceToHost, w->stream)) != hipSuccess ||
@@ -2174,13 +2230,7 @@ static int collective_verify_pipelined(bftkv_gpu_ctx* c, int quorum, uint32_t n_
       first_rc = fail(c, BFTKV_E_DEVICE, "host-buffer pipeline: second pass of a piece", e);
     tr[6] += 1.f;
   }
-  if (first_rc) {      // fail closed: no byte of the result reads as "verified"
-    if (err_out) memset(err_out, BFTKV_ERR_INSUFFICIENT_SIGNATURES, n_items);
-    if (verdict_out) memset(verdict_out, 0, n_items);
-    if (nver_out) memset(nver_out, 0, sizeof(uint32_t) * (size_t)n_items);
-    if (fenced_out) memset(fenced_out, 0, n_items);
-    return first_rc;
-  }
+  if (first_rc) { fail_closed(n_items, err_out, nver_out, verdict_out, fenced_out); return first_rc; }
   if (err_out) memcpy(err_out, c->hb_out + o_err, n_items);
   if (verdict_out) memcpy(verdict_out, c->hb_out + o_vd, n_items);
   if (fenced_out) memcpy(fenced_out, c->hb_out + o_fn, n_items);
@@ -2205,39 +2255,7 @@ static int collective_verify_pipelined(bftkv_gpu_ctx* c, int quorum, uint32_t n_
 
 static int collective_verify_host(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off,
                                   const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
-                                  uint8_t* verdict_out, uint8_t* fenced_out, const HbSeg* sg = nullptr);
-
-int bftkv_gpu_collective_verify(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off,
-                                const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
-                                uint8_t* verdict_out, uint8_t* fenced_out) {
-  const int rc = collective_verify_host(c, quorum, n_items, tbs, tbs_off, ss, ss_off, err_out, nver_out, verdict_out, fenced_out);
-  if (rc && n_items) {     // fail closed on EVERY path: no byte of the caller's arrays reads as "verified" beside a non-zero return code
-    if (err_out) memset(err_out, BFTKV_ERR_INSUFFICIENT_SIGNATURES, n_items);
-    if (verdict_out) memset(verdict_out, 0, n_items);
-    if (nver_out) memset(nver_out, 0, sizeof(uint32_t) * (size_t)n_items);
-    if (fenced_out) memset(fenced_out, 0, n_items);
-  }
-  return rc;
-}
-
-int bftkv_gpu_collective_verify_segments(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* prefix, const uint64_t* prefix_off,
-                                         const uint8_t* shared, const uint64_t* shared_off, uint32_t n_shared, const uint32_t* seg_of_item,
-                                         const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
-                                         uint8_t* verdict_out, uint8_t* fenced_out) {
-  const HbSeg sg{prefix, prefix_off, shared, shared_off, n_shared, seg_of_item};
-  const int rc = collective_verify_host(c, quorum, n_items, nullptr, nullptr, ss, ss_off, err_out, nver_out, verdict_out, fenced_out, &sg);
-  if (rc && n_items) {     // fail closed, as bftkv_gpu_collective_verify
-    if (err_out) memset(err_out, BFTKV_ERR_INSUFFICIENT_SIGNATURES, n_items);
-    if (verdict_out) memset(verdict_out, 0, n_items);
-    if (nver_out) memset(nver_out, 0, sizeof(uint32_t) * (size_t)n_items);
-    if (fenced_out) memset(fenced_out, 0, n_items);
-  }
-  return rc;
-}
-
-static int collective_verify_host(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off,
-                                  const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
-                                  uint8_t* verdict_out, uint8_t* fenced_out, const HbSeg* sg) {
+                                  uint8_t* verdict_out, uint8_t* fenced_out, const HbSeg* sg = nullptr) {
   if (!c || (n_items && (!ss_off || (!sg && !tbs_off)))) return BFTKV_E_INVALID;
   if (sg && n_items && (!sg->prefix_off || !sg->seg || (sg->n_shared && (!sg->shared_off || (!sg->shared && sg->shared_off[sg->n_shared]))))) return BFTKV_E_INVALID;
   if (n_items == 0) return 0;
@@ -2308,9 +2326,11 @@ static int collective_verify_host(bftkv_gpu_ctx* c, int quorum, uint32_t n_items
     if (!c->seg_ev) HIPCHK(c, hipEventCreateWithFlags(&c->seg_ev, hipEventDisableTiming));
     HIPCHK(c, hipEventRecord(c->seg_ev, c->stream));
   }
-  int rc = collective_verify_impl(c, quorum, n_items, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>(), c->in_ss.as<uint8_t>(),
-                                  c->in_ss_off.as<uint64_t>(), c->o_err.as<uint8_t>(), c->o_nver.as<uint32_t>(), c->o_verdict.as<uint8_t>(),
-                                  fenced_out ? c->o_fenced.as<uint8_t>() : nullptr, &upload_tbs, sl);
+  PipelineCall call;
+  call.n_items = n_items; call.d_tbs = c->in_tbs.as<uint8_t>(); call.d_tbs_off = c->in_tbs_off.as<uint64_t>();
+  call.d_ss = c->in_ss.as<uint8_t>(); call.d_ss_off = c->in_ss_off.as<uint64_t>(); call.ss_len = sl; call.upload_tbs = &upload_tbs;
+  int rc = collective_verify_impl(c, quorum, call, c->o_err.as<uint8_t>(), c->o_nver.as<uint32_t>(), c->o_verdict.as<uint8_t>(),
+                                  fenced_out ? c->o_fenced.as<uint8_t>() : nullptr);
   if (rc) return rc;
   if (fenced_out) HIPCHK(c, hipMemcpyAsync(fenced_out, c->o_fenced.p, n_items, hipMemcpyDeviceToHost, c->stream));
   if (err_out) HIPCHK(c, hipMemcpyAsync(err_out, c->o_err.p, n_items, hipMemcpyDeviceToHost, c->stream));
@@ -2318,6 +2338,24 @@ static int collective_verify_host(bftkv_gpu_ctx* c, int quorum, uint32_t n_items
   if (verdict_out) HIPCHK(c, hipMemcpyAsync(verdict_out, c->o_verdict.p, n_items, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
+}
+
+int bftkv_gpu_collective_verify(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* tbs, const uint64_t* tbs_off,
+                                const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
+                                uint8_t* verdict_out, uint8_t* fenced_out) {
+  const int rc = collective_verify_host(c, quorum, n_items, tbs, tbs_off, ss, ss_off, err_out, nver_out, verdict_out, fenced_out);
+  if (rc && n_items) fail_closed(n_items, err_out, nver_out, verdict_out, fenced_out);      // on EVERY path
+  return rc;
+}
+
+int bftkv_gpu_collective_verify_segments(bftkv_gpu_ctx* c, int quorum, uint32_t n_items, const uint8_t* prefix, const uint64_t* prefix_off,
+                                         const uint8_t* shared, const uint64_t* shared_off, uint32_t n_shared, const uint32_t* seg_of_item,
+                                         const uint8_t* ss, const uint64_t* ss_off, uint8_t* err_out, uint32_t* nver_out,
+                                         uint8_t* verdict_out, uint8_t* fenced_out) {
+  const HbSeg sg{prefix, prefix_off, shared, shared_off, n_shared, seg_of_item};
+  const int rc = collective_verify_host(c, quorum, n_items, nullptr, nullptr, ss, ss_off, err_out, nver_out, verdict_out, fenced_out, &sg);
+  if (rc && n_items) fail_closed(n_items, err_out, nver_out, verdict_out, fenced_out);
+  return rc;
 }
 
 // Signature.Verify over a batch with the keyring of item i restricted to entity index ent[i] (0xFFFFFFFF: the node
@@ -2360,8 +2398,11 @@ int signature_verify_entities(bftkv_gpu_ctx* c, uint32_t n_items, const uint8_t*
     HIPCHK(c, hipMemcpyAsync(c->forced_iss.p, forced_issuer, sizeof(uint64_t) * n_items, hipMemcpyHostToDevice, c->stream));
     d_forced = c->forced_iss.as<uint64_t>();
   }
-  int rc = run_pipeline(c, n_items, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>(), c->in_ss.as<uint8_t>(),
-                        c->in_ss_off.as<uint64_t>(), d_cert, d_cls, nullptr, nullptr, nullptr, nullptr, sl, nullptr, nullptr, 0, nullptr, false, d_forced);
+  PipelineCall call;
+  call.n_items = n_items; call.d_tbs = c->in_tbs.as<uint8_t>(); call.d_tbs_off = c->in_tbs_off.as<uint64_t>();
+  call.d_ss = c->in_ss.as<uint8_t>(); call.d_ss_off = c->in_ss_off.as<uint64_t>(); call.ss_len = sl;
+  call.d_cert_ent = d_cert; call.d_sig_class = d_cls; call.d_forced_issuer = d_forced;
+  int rc = run_pipeline(c, call);
   if (rc) return rc;
   hipLaunchKernelGGL(k_sigverify_fold, dim3((n_items + 255) / 256), dim3(256), 0, c->stream, c->recs.as<SigRec>(),
                      c->base.as<uint32_t>(), c->counts.as<uint32_t>(), c->item_flags.as<uint8_t>(), n_items, c->o_err.as<uint8_t>());

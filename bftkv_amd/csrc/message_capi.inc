@@ -249,8 +249,12 @@ extern "C" int bftkv_gpu_message_verify(bftkv_gpu_ctx* c, uint32_t n_msgs, const
     HIPCHK(c, hipMemcpyAsync(c->in_ss_off.p, v_sig_off.data(), sizeof(uint64_t) * (n_items + 1), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->cert_ent.p, v_slot.data(), sizeof(uint32_t) * n_items, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->sig_class.p, v_hash.data(), n_items, hipMemcpyHostToDevice, s));
-    int rc = run_pipeline(c, n_items, c->in_tbs.as<uint8_t>(), c->in_tbs_off.as<uint64_t>(), c->in_ss.as<uint8_t>(), c->in_ss_off.as<uint64_t>(),
-                          nullptr, nullptr, c->cert_ent.as<uint32_t>(), c->sig_class.as<uint8_t>());
+    PipelineCall call;
+    call.n_items = n_items; call.d_tbs = c->in_tbs.as<uint8_t>(); call.d_tbs_off = c->in_tbs_off.as<uint64_t>();
+    call.d_ss = c->in_ss.as<uint8_t>(); call.d_ss_off = c->in_ss_off.as<uint64_t>();
+    // (the certificate calls' buffers, reused: a message call has neither an entity nor a signature class per item)
+    call.d_msg_slot = c->cert_ent.as<uint32_t>(); call.d_msg_hash = c->sig_class.as<uint8_t>();
+    int rc = run_pipeline(c, call);
     if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev[4], s));
     c->have_timing = true;

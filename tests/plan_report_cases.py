@@ -113,8 +113,9 @@ def make_batches(cl, signer):
     return out
 
 
-def run_resident(ctx, qh, batch):
-    """One bftkv_gpu_collective_verify_dev call over device-resident inputs; everything a test compares, as numpy arrays."""
+def run_resident(ctx, qh, batch, report=True):
+    """One bftkv_gpu_collective_verify_dev call over device-resident inputs; everything a test compares, as numpy arrays.
+    report=False: a call below the big path, which the plan-report getter does not describe."""
     import torch
     tb, to, sb, so = batch
     n = len(to) - 1
@@ -133,7 +134,7 @@ def run_resident(ctx, qh, batch):
                               err.data_ptr(), nver.data_ptr(), verdict.data_ptr(), fenced.data_ptr())
     ctx.sync()
     st, st_item = ctx.last_statuses()
-    rep = ctx.last_plan_report()
+    rep = ctx.last_plan_report() if report else dict.fromkeys(ctx.PLAN_REPORT_SLOTS, 0)
     ops = ctx.last_counters()["pubkey_ops"]
     return {"err": err.cpu().numpy(), "nver": nver.cpu().numpy().astype(np.uint32), "verdict": verdict.cpu().numpy(),
             "fenced": fenced.cpu().numpy(), "st": st.copy(), "st_item": st_item.copy(),

@@ -227,3 +227,60 @@ def test_server_write_verify_sends_each_certificate_once(gpu_ctx):
         r = col.collective_verify(kr, c.tbss(i), SignaturePacket(Type=1, Data=c.ss_data(i) or None), q)
         assert (err[i] == 0) == (r.err is None), i
     assert 0 < int((np.array(err) == 0).sum()) < c.n_items
+
+
+def test_small_pieces_under_the_early_exit_verify_behind_their_cut_on_eight_lanes(gpu_ctx):
+    """A piece of a pipelined call with few signature bytes (at most 2 MB) puts its main modexp pass on eight lanes per number, and
+    under the early exit it plans in two phases: phase 2's modexp grid is then sized by the 8-lane block.  A 64-replica clique, 60
+    writes in two forced pieces of about 0.5 MB of signature streams each; every third item has two bad values among its first
+    three packets, one more than the plan's margin absorbs, so it is admitted only by what phase 2 verifies.  Judged by the C
+    restatement of the reference on error byte and verified count, and equal to the same batch through the resident entry.
+    What this does and does not pin: that the combination runs and phase 2 verifies behind the cut in it.  NOT the grid: a piece's
+    grids cover its packet bound (about 12,000 here, for about 1,750 packets of which phase 2 queues about 140), so a phase-2
+    grid of half the blocks would still cover the work; and that the 8-lane form is taken follows from the size asserted below
+    and BFTKV_NO_WIDE8 being unset, not from anything read back.  The grid itself is held by the traced comparison of launches
+    against the parent (docs/history.md, 2026-10-21)."""
+    from oracle import collective as col
+    from oracle.cbind import COracle
+    from oracle.packet import SignaturePacket
+    from tests import plan_report_cases as K
+    cl = cb.make_cluster(64)
+    mods, exps = cb.signer_tables(cl)
+    signer = lambda em, ki: gpu_ctx.modexp(em, ki.astype(np.uint32), mods, exps)
+    c = cb.make_write_corpus(cl, 60, seed=cb.MASTER_SEED + 12, min_sigs=cl.suff + 8, batch_signer=signer, with_client_sig=True, mutation_rates={})
+    ss = K.streams(c)
+    twice = [i for i in range(c.n_items) if i % 3 == 0]
+    for i in twice:
+        assert len(ss[i]) % K.PKT == 0 and len(ss[i]) // K.PKT >= cl.suff + 4
+        p = [ss[i][j:j + K.PKT] for j in range(0, len(ss[i]), K.PKT)]
+        p[0], p[2] = K.flip_value(p[0]), K.flip_value(p[2])
+        ss[i] = b"".join(p)
+    sb, so = K.cat(ss)
+    assert 900_000 < int(so[-1]) < 4 << 20      # (each of two pieces: at most 8192 x 256 bytes, the 8-lane form's limit)
+    kr, q = H.oracle_keyring(cl), H.clique_quorum(cl)
+    co = COracle()
+    co.set_keyring(kr)
+    co.set_quorum(q)
+    want_err, want_nver, _ = co.collective_verify(c.tbss_blob, c.tbss_off, sb, so, n_threads=max(1, min(16, __import__("os").cpu_count() or 1)))
+    assert (want_err == 0).all()
+    # on the CPU first: phase 1 cuts an item where the tally would become sufficient plus a margin of 1 + suff / 64 packets
+    # (k_plan<1>); up to that cut such an item is short, so it is admitted only from the packets behind it
+    cut = cl.suff + 1 + cl.suff // 64
+    i = twice[1]
+    upto_cut = col.collective_verify(kr, c.tbss(i), SignaturePacket(Type=1, Data=ss[i][:cut * K.PKT]), q)
+    whole = col.collective_verify(kr, c.tbss(i), SignaturePacket(Type=1, Data=ss[i]), q)
+    assert upto_cut.err is not None and len(upto_cut.verified) == cut - 2 and whole.err is None
+    gpu_ctx.keyring_set(H.abi_keys(kr))
+    qh = gpu_ctx.quorum_create(H.abi_qcs(q))
+    gpu_ctx.set_early_exit(True)
+    try:
+        gpu_ctx.set_host_pipeline(2)
+        err, nver, _ = gpu_ctx.collective_verify(qh, c.tbss_blob, c.tbss_off, sb, so)
+        tr = gpu_ctx.host_pipeline_trace()
+        assert tr["pieces"] == 2 and tr["second_passes"] == 0
+        assert np.array_equal(err, want_err) and np.array_equal(nver, want_nver)
+        res = K.run_resident(gpu_ctx, qh, (c.tbss_blob, c.tbss_off, sb, so), report=False)
+        assert np.array_equal(res["err"], err) and np.array_equal(res["nver"], nver)
+    finally:
+        gpu_ctx.set_host_pipeline(0)
+        gpu_ctx.quorum_destroy(qh)
